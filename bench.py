@@ -16,6 +16,14 @@ owns a contiguous shard of trajectories.
 `--workload time` runs config 5 instead (time-allocation optimisation, 50
 objective evaluations per trajectory, B=4096); `--workload tube` config 3
 (tube QCQP, B=4096).
+
+A plain run sets up, warms up, times the K steps and prints the line.
+`--full` adds the measurements that take runs of their own: the CPU baseline
+(`cpu_baseline`, off again with --no-cpu-baseline) and, for the linear
+workload on one GPU, the selection-inclusive step
+(`config.selection_step_ms`).  `--dump-outputs DIR` writes what the last
+timed step computed as DIR/<name>.npy (float64), for comparing two builds
+output for output.
 """
 import argparse
 import json
@@ -44,7 +52,15 @@ def parse():
     p.add_argument("--cpu-seconds", type=float, default=20.0,
                    help="total CPU-baseline budget (all reps, both modes)")
     p.add_argument("--cpu-reps", type=int, default=5)
-    p.add_argument("--no-cpu-baseline", action="store_true")
+    p.add_argument("--no-cpu-baseline", action="store_true",
+                   help="with --full: leave the CPU baseline out")
+    p.add_argument("--full", action="store_true",
+                   help="also run what the headline figure does not need: the CPU baseline "
+                        "and, for the linear workload on one GPU, the selection-inclusive step")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="after the timed steps, write the arrays the last timed step computed "
+                        "as DIR/<name>.npy (float64; a fixed, seeded sample of outputs above "
+                        "60 MB in all)")
     p.add_argument("--no-graph", action="store_true", help="eager launches (no HIP graph)")
     p.add_argument("--select", action="store_true",
                    help="linear: include the device selection step (RCCL all-gather + argmin, "
@@ -463,20 +479,67 @@ def config_name(wl, B, world, S, global_batch=None):
     return f"{wl}: {B} x {S}-segment per GPU"
 
 
+MAX_GRAPH_STEPS = 8192  # steps per captured graph when --graph-chunk leaves it open
+
+
 def graph_chunks(k, head, chunk):
     """Sizes of the graphs the K timed steps are captured into, in replay
     order: `head` steps first (0: none), then graphs of `chunk` steps (0: the
-    rest in one graph).  Smaller first graphs let the device start while the
-    host still submits the later ones."""
+    rest in one graph, up to MAX_GRAPH_STEPS per graph).  Smaller first
+    graphs let the device start while the host still submits the later ones.
+    The cap keeps a graph's chain of kernel nodes bounded however large K is:
+    one graph of 400 000 steps ended the process with a segmentation fault in
+    the HIP runtime where 40 000 ran.  Graphs of equal size are captured once
+    and replayed (main), so a large K costs two captures, not K / chunk."""
     sizes = []
     if 0 < head < k:
         sizes.append(head)
     rest = k - sum(sizes)
-    c = chunk if chunk > 0 else rest
+    c = chunk if chunk > 0 else min(rest, MAX_GRAPH_STEPS)
     while rest > 0:
         sizes.append(min(c, rest))
         rest -= sizes[-1]
     return sizes
+
+
+DUMP_BUDGET_BYTES = 60 * 10 ** 6  # of array data; the .npy headers stay well under 64 MB in all
+
+
+def named_outputs(wl, ret):
+    """The arrays a caller of the timed step receives, by name: the step's
+    dict, or the (samples, sample_times, n_samples) of the sampling workload
+    with the columns past each trajectory's sample count (left unset by the
+    kernel) zeroed."""
+    if wl == "sample":
+        smp, stm, cnt = ret
+        import torch
+        keep = torch.arange(smp.shape[-1], device=smp.device)[None, :] < cnt[:, None]
+        zero = torch.zeros((), dtype=smp.dtype, device=smp.device)
+        return {"samples": torch.where(keep[:, None, :], smp, zero),
+                "sample_times": torch.where(keep, stm, zero), "n_samples": cnt}
+    return {k: v for k, v in ret.items() if v is not None}
+
+
+def dump_outputs(dirpath, arrays, rank=0, world=1):
+    """Write each tensor as dirpath/<name>.npy in float64 (<name>.rank<r>.npy
+    on several GPUs).  Above DUMP_BUDGET_BYTES in all, every array keeps the
+    same share of its elements: a sorted sample of the flattened array drawn
+    with a fixed seed, so two runs with the same arguments keep the same
+    elements."""
+    import torch
+    os.makedirs(dirpath, exist_ok=True)
+    total = sum(t.numel() for t in arrays.values()) * 8
+    share = min(1.0, DUMP_BUDGET_BYTES / max(total, 1))
+    for j, name in enumerate(sorted(arrays)):
+        t = arrays[name].detach()
+        if share < 1.0:
+            n = t.numel()
+            idx = np.sort(np.random.default_rng(1000 + j).choice(n, max(1, int(n * share)),
+                                                                  replace=False))
+            t = t.reshape(-1)[torch.from_numpy(idx).to(t.device)]
+        a = t.to(torch.float64).cpu().numpy()
+        suffix = ".npy" if world == 1 else f".rank{rank}.npy"
+        np.save(os.path.join(dirpath, name + suffix), a)
 
 
 def launch_ranks(n, argv, port=None):
@@ -626,6 +689,9 @@ def main():
         if pipe is not None:
             pipe.drain()
 
+    def step_outputs(ret):  # --dump-outputs: the last timed step's arrays by name
+        return named_outputs(wl, ret)
+
     if wl == "linear":
         out = plan.solve(fixed_d, times_d, free=False)
         shard_start = shard_range(global_batch, world, rank)[0]
@@ -649,6 +715,11 @@ def main():
                 return step_selected()
             plan.solve(fixed_d, times_d, free=False, out=out)
             return None
+
+        def step_outputs(ret):
+            if select:  # the last step's output set and the bucket's winners
+                return {**pipe.outs[(pipe.k - 1) % 2], "best": pipe.best[:pipe.n_done]}
+            return out
 
         bytes_per_traj = (D * nf + S) * 8 + (S * D * N + 1) * 8 + 4  # + status
         metric = metric_base
@@ -885,6 +956,7 @@ def main():
     # them.
     use_graph = not args.no_graph
     graphs = {}
+    last_ret = None  # what the last timed step returned (in a graph: filled by the replay)
     if select:  # communicator set up and first collectives outside any capture
         with stdout_to_stderr():
             for _ in range(max(args.warmup, 2)):
@@ -895,18 +967,22 @@ def main():
     if use_graph:
         capture_error = None
         try:  # capture only: nothing executes (no collective runs) here
-            for name, sizes in (("warmup", [args.warmup]),
+            for name, sizes in (("warmup", graph_chunks(args.warmup, 0, 0) or [0]),
                                 ("timed", graph_chunks(args.steps, args.graph_head,
                                                        args.graph_chunk))):
-                gl = []
+                by_size = {}  # graphs of equal size: captured once, replayed
                 for n in sizes:
+                    if n in by_size:
+                        continue
                     g = torch.cuda.CUDAGraph()
+                    ret = None
                     with torch.cuda.graph(g):
                         for _ in range(n):
-                            step()
+                            ret = step()
                         end_steps()
-                    gl.append(g)
-                graphs[name] = gl
+                    by_size[n] = (g, ret)
+                graphs[name] = [by_size[n][0] for n in sizes]
+                last_ret = by_size[sizes[-1]][1] if sizes else None
         except Exception as exc:
             capture_error = f"{type(exc).__name__}: {exc}"
         if world > 1:
@@ -953,7 +1029,7 @@ def main():
         t0 = time.perf_counter()
         for i in range(args.steps):
             ev[i][0].record(stream)
-            step()
+            last_ret = step()
             ev[i][1].record(stream)
         end_steps()
         torch.cuda.synchronize(dev)
@@ -967,11 +1043,14 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
 
-    # One GPU: also time the selection-inclusive step (the step every rank runs
-    # at --gpus > 1, minus the all-gather), so the scaling curve's N = 1 and
-    # N > 1 points can be compared step for step.
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, step_outputs(last_ret), rank, world)
+
+    # --full, one GPU: also time the selection-inclusive step (the step every
+    # rank runs at --gpus > 1, minus the all-gather), so the scaling curve's
+    # N = 1 and N > 1 points can be compared step for step.
     selection_ms = None
-    if wl == "linear" and not select:
+    if args.full and wl == "linear" and not select:
         for _ in range(3):
             step_selected()
         end_steps()
@@ -1055,7 +1134,7 @@ def main():
 
     if rank == 0:
         cpu = None
-        if not args.no_cpu_baseline and world == 1:
+        if args.full and not args.no_cpu_baseline and world == 1:
             if wl == "collision":
                 cpu = cpu_baseline_collision(N, r, coll, args.cpu_seconds, args.cpu_reps)
             else:

@@ -45,6 +45,68 @@ def _bench_module():
     return mod
 
 
+def test_plain_run_options():
+    """--full (off by default) gates the CPU baseline and the selection step;
+    --dump-outputs names the directory of the last timed step's arrays."""
+    b = _bench_module()
+    argv = sys.argv
+    try:
+        sys.argv = ["bench.py", "--gpus", "1", "--steps", "7", "--warmup", "2"]
+        a = b.parse()
+        assert (a.full, a.dump_outputs, a.steps, a.warmup) == (False, None, 7, 2)
+        sys.argv += ["--full", "--dump-outputs", "d"]
+        a = b.parse()
+        assert (a.full, a.dump_outputs) == (True, "d")
+    finally:
+        sys.argv = argv
+    # --steps K is K timed steps, in one graph up to the cap and in graphs of
+    # the cap (one capture, replayed) and one remainder above it
+    assert b.graph_chunks(7, 0, 0) == [7] and b.graph_chunks(7, 2, 3) == [2, 3, 2]
+    assert b.graph_chunks(200, 0, 0) == [200]
+    cap = b.MAX_GRAPH_STEPS
+    assert b.graph_chunks(cap, 0, 0) == [cap]
+    big = b.graph_chunks(400000, 0, 0)
+    assert sum(big) == 400000 and max(big) == cap and len(set(big)) == 2
+    assert b.graph_chunks(0, 0, 0) == []
+
+
+def test_dump_outputs(tmp_path):
+    """Every array goes out as <name>.npy in float64 with its values; above
+    the byte budget each keeps the same seeded sample of its elements from
+    call to call."""
+    import numpy as np
+    import torch
+    b = _bench_module()
+    arrays = {"coeffs": torch.arange(240, dtype=torch.float64).reshape(2, 4, 3, 10) / 7,
+              "cost": torch.tensor([1.5, float("nan")], dtype=torch.float64),
+              "status": torch.tensor([0, -5], dtype=torch.int32)}
+    d = tmp_path / "whole"
+    b.dump_outputs(str(d), arrays)
+    assert sorted(os.listdir(d)) == ["coeffs.npy", "cost.npy", "status.npy"]
+    for name, t in arrays.items():
+        a = np.load(d / f"{name}.npy")
+        assert a.dtype == np.float64 and a.shape == tuple(t.shape)
+        np.testing.assert_array_equal(a, t.to(torch.float64).numpy())
+
+    budget = b.DUMP_BUDGET_BYTES
+    b.DUMP_BUDGET_BYTES = 488  # a quarter of the 244 x 8 bytes
+    try:
+        b.dump_outputs(str(tmp_path / "s1"), arrays)
+        b.dump_outputs(str(tmp_path / "s2"), arrays)
+    finally:
+        b.DUMP_BUDGET_BYTES = budget
+    total = 0
+    for name, t in arrays.items():
+        s1, s2 = np.load(tmp_path / "s1" / f"{name}.npy"), np.load(tmp_path / "s2" / f"{name}.npy")
+        np.testing.assert_array_equal(s1, s2)
+        assert s1.ndim == 1 and 1 <= s1.size <= max(1, t.numel() // 4)
+        flat = t.to(torch.float64).numpy().ravel()
+        assert np.isin(s1[~np.isnan(s1)], flat).all()
+        total += s1.nbytes
+    assert total <= 488 + 8 * len(arrays)
+    assert np.load(tmp_path / "s1" / "coeffs.npy").size == 60
+
+
 def test_profiled_entry_guard():
     """Committed PMC / SQ entries are used only when their profiled kernel
     time can come from this build: within 15 % of the run's, plus the

@@ -4,7 +4,7 @@
 set -e -o pipefail
 mkdir -p gpurun_out
 export TMPDIR=/tmp
-B() { timeout -k 10 300 python bench.py "$@"; }
+B() { timeout -k 10 300 python bench.py --full "$@"; }
 B > gpurun_out/bench_linear.json 2> gpurun_out/bench_linear.err
 B --workload tube --steps 20 --warmup 3 > gpurun_out/bench_tube.json 2> gpurun_out/bench_tube.err
 B --workload time-qcqp --steps 5 --warmup 1 > gpurun_out/bench_time_qcqp.json 2> gpurun_out/bench_time_qcqp.err

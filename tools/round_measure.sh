@@ -33,7 +33,9 @@
 set -e -o pipefail
 mkdir -p gpurun_out
 export TMPDIR=/tmp
-B() { timeout -k 10 300 python bench.py "$@"; }
+# the recorded lines carry the CPU baseline (unless --no-cpu-baseline) and the
+# selection-inclusive step: both are behind bench.py's --full
+B() { timeout -k 10 300 python bench.py --full "$@"; }
 kline() {  # <json> <tag>: kernel_ms and ms_per_step of a bench line
   python3 -c "import json,sys; d=json.load(open(sys.argv[1])); print(sys.argv[2], 'kernel', round(d['roofline']['kernel_ms']*1e3,3), 'us  step', round(d['ms_per_step']*1e3,3), 'us')" "$1" "$2"
 }
