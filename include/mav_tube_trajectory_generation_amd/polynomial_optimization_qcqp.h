@@ -22,6 +22,11 @@
 // -R_pf d_f instead of the solution to the free derivatives
 // (qcqp_impl:246-247); here solveLinear returns the unconstrained minimiser
 // for the tube pattern (the QCQP without inequality constraints).
+//
+// Deliberate difference: the device solves the QCQP in coordinates relative
+// to the midpoint of the first and last vertex (mtg_hip.h, tube section), so
+// the result does not depend on where the world origin is; the reference's
+// snap of |b| < 1e-6 (qcqp_impl:388-400) acts on the relative b.
 #ifndef MAV_TUBE_TRAJECTORY_GENERATION_AMD_POLYNOMIAL_OPTIMIZATION_QCQP_H_
 #define MAV_TUBE_TRAJECTORY_GENERATION_AMD_POLYNOMIAL_OPTIMIZATION_QCQP_H_
 

@@ -402,6 +402,13 @@ int mtg_time_free_optimize_ex(const mtg_plan* plan, int64_t B, const double* fix
  * retried once with a 1e-10 relative diagonal regularisation before the
  * solve stops (MTG_TRAJ_NOT_SPD when away from the optimum).  B < 2^26 (one 64-lane workgroup per
  * trajectory).
+ *
+ * Every tube entry point works in coordinates relative to the midpoint of
+ * the trajectory's first and last vertex (positions, the fixed end positions
+ * and an input x are shifted on load; the positions in the output x and the
+ * constant coefficients are shifted back), so results do not depend on where
+ * the world origin is.  The reference's snap of |b| < 1e-6 to zero
+ * (qcqp_impl:388-400) acts on the relative b.
  */
 int mtg_tube_num_constraints(int N, int S);
 int mtg_tube_residuals(mtg_ctx* ctx, int N, int r, int S, int64_t B,

@@ -38,7 +38,9 @@ __global__ __launch_bounds__(kWave) void tube_residuals_kernel(
   for (int idx = t.tid; idx < n; idx += t.nthr) {
     // reference order d*(S-1)*M + (u-1)*M + m  ->  internal ((u-1)*3+d)*M + m
     const int d = idx / ((S - 1) * M), a = (idx / M) % (S - 1), m = idx % M;
-    smem[L.x + (a * 3 + d) * M + m] = x[b * n + idx];
+    // positions relative to tube_origin(), as Tube::setup holds them
+    const double o = m == 0 ? tube_origin(positions, b / rep, S, d) : 0.0;
+    smem[L.x + (a * 3 + d) * M + m] = x[b * n + idx] - o;
   }
   __syncthreads();
   t.control_points(smem + L.x, L.cp);
@@ -100,11 +102,15 @@ __device__ __attribute__((always_inline)) void tube_solve_body(
   __syncthreads();
   // Outputs: x (reference order), coefficients (qcqp_impl:777-785 ->
   // linear_impl:254-275) and computeCost (linear_impl:113-130).
+  // The solve is relative to tube_origin() (Tube::setup): x's positions and
+  // the constant coefficients go back to world coordinates; the cost is the
+  // relative problem's (a translation does not change it).
   const int n = t.nv * 3 * M;
   if (x_out)
     for (int idx = t.tid; idx < n; idx += t.nthr) {
       const int d = idx / ((S - 1) * M), a = (idx / M) % (S - 1), m = idx % M;
-      x_out[b * n + idx] = no_x ? NAN : smem[L.x + (a * 3 + d) * M + m];
+      const double v = smem[L.x + (a * 3 + d) * M + m];
+      x_out[b * n + idx] = no_x ? NAN : (m == 0 ? v + tube_origin(positions, b / rep, S, d) : v);
     }
   const double* xv = smem + L.x;
   double acc = 0.0;
@@ -120,7 +126,7 @@ __device__ __attribute__((always_inline)) void tube_solve_body(
       c += tab[N * N + k * N + j] * t.pwr(s, l - k) * e;
       h += tab[k * N + j] * t.pwr(s, 1 - 2 * r + lk + l) * e;
     }
-    coeffs[b * per + i] = no_x ? NAN : c;
+    coeffs[b * per + i] = no_x ? NAN : (k == 0 ? c + tube_origin(positions, b / rep, S, d) : c);
     acc += h * t.xval(xv, s + k / M, d, lk);
   }
   const double J = 0.5 * t.block_sum(acc);

@@ -60,6 +60,18 @@ struct TubeLayout {
 
 constexpr int kGeo = 19;  // n[3] LL[9] L[3] mu n.ps n.pe r2^2
 
+// Coordinate d of the point a trajectory's tube problem is solved relative
+// to: the midpoint of its first and last vertex.  It moves with the
+// trajectory, so the solve does not depend on where the world origin is,
+// and it is the same point for the trajectory flown backwards (the first
+// vertex alone is not: the reversed problem would start from another
+// slack scale and |q|).  The oracle uses the same point (setupTube).
+__device__ inline double tube_origin(const double* __restrict__ positions, int64_t bin, int S,
+                                     int d) {
+  const double* p = positions + bin * (S + 1) * 3;
+  return 0.5 * (p[d] + p[S * 3 + d]);
+}
+
 __host__ __device__ inline int tube_ncon(int N, int S) { return (S - 1) + 3 * S * (N - 2); }
 
 __host__ __device__ inline TubeLayout make_tube_layout(int N, int S) {
@@ -195,11 +207,19 @@ struct Tube {
                         const double* __restrict__ radii, int* bad) {
     const int NN = N * N;
     for (int i = tid; i < S; i += nthr) sm[L->T + i] = times[b * S + i];
-    for (int i = tid; i < (S + 1) * 3; i += nthr) sm[L->pos + i] = positions[bin * (S + 1) * 3 + i];
+    // Positions are held relative to tube_origin(): the expanded tube form
+    // below (mu = |b|^2 - r1^2, with the reference's snap of |b| < 1e-6
+    // acting on the relative b), q, the cold start's slack scale and the
+    // stopping test of ipm() then do not depend on where the world origin
+    // is.  The callers shift x the same way on input and shift x and the
+    // constant coefficients back on output.
+    for (int i = tid; i < (S + 1) * 3; i += nthr)
+      sm[L->pos + i] = positions[bin * (S + 1) * 3 + i] - tube_origin(positions, bin, S, i % 3);
     for (int i = tid; i < 3 * N; i += nthr) {
       // fixed_vals[d][end*M + m] -> fixv[end][d][m]
       const int d = i / N, e = (i % N) / M, m = i % M;
-      sm[L->fixv + (e * 3 + d) * M + m] = fixed_vals[bin * 3 * N + i];
+      const double v = fixed_vals[bin * 3 * N + i];
+      sm[L->fixv + (e * 3 + d) * M + m] = m == 0 ? v - tube_origin(positions, bin, S, d) : v;
     }
     if (tid == 0) *bad = 0;
     __syncthreads();
@@ -1064,8 +1084,9 @@ struct Tube {
     }
     control_points(sm + L->x, L->cp);
     // Start scaled to the problem (the oracle's rule): slacks at least the
-    // square of the largest vertex coordinate (the constraints are in squared
-    // lengths), multipliers at least kLamStart |q|_inf.
+    // square of the largest vertex coordinate (relative to tube_origin(), so
+    // the trajectory's extent; the constraints are in squared lengths),
+    // multipliers at least kLamStart |q|_inf.
     double pm = 1.0;
     for (int i = tid; i < (S + 1) * 3; i += nthr) pm = fmax(pm, fabs(sm[L->pos + i]));
     pm = block_max(pm);

@@ -591,6 +591,17 @@ struct TubeProblem {
   std::vector<double> dfk;   // fixed_constraints_compact_kDim_
   std::vector<int> col1;     // 1-D reordering rows -> columns
   std::vector<QConstraint> cons;
+  // The problem is held relative to this point (setupTube: the midpoint of
+  // the first and last vertex, or zero): positions in, x and the constant
+  // coefficients out.
+  std::vector<double> origin;
+
+  // Position entries (derivative 0) of a free-variable vector, x[d][v][m].
+  void shiftPositions(std::vector<double>* x, double sign) const {
+    const int h = N / 2;
+    for (int d = 0; d < D; ++d)
+      for (int v = 0; v < S - 1; ++v) (*x)[(d * (S - 1) + v) * h] += sign * origin[d];
+  }
 
   // qcqp_impl:121-186 + :18-118.
   int setup(const std::vector<Vertex>& vs, const std::vector<double>& times_cp,
@@ -904,7 +915,8 @@ struct TubeProblem {
       }
     }
     // Cold start scaled to the problem (round 6): slacks at least the square
-    // of the largest vertex coordinate (the constraints' units are squared
+    // of the largest vertex coordinate (relative to the origin of setupTube,
+    // so the trajectory's extent; the constraints' units are squared
     // lengths), multipliers at least 30 |q|_inf (the objective's gradient
     // scale).  Unit slacks and multipliers started the iteration far below
     // both scales: 30.6 -> 21.6 IPM iterations on 400 C3 problems, the same
@@ -1095,10 +1107,30 @@ struct TubeProblem {
   }
 };
 
+// relative: the problem is built in coordinates relative to the midpoint of
+// the first and last vertex (the device's rule, tube_origin()), so that
+// neither the expanded constraint forms (|b|^2 - r1^2, |p|^2 - r2^2) nor the
+// cold start and stopping test of solveIPM depend on where the world origin
+// is.  The midpoint, not the first vertex: it is also the same point for the
+// trajectory flown backwards, so pmax and |q| of the reversed problem are
+// the same (with the first vertex, seed 105 at S = 10 took 26 iterations
+// forwards and 22 backwards).  The reference's snap of |b| < 1e-6 to zero
+// (qcqp_impl:388-400) then acts on the relative b.  orc_tube_qcqp_assemble
+// keeps the reference's absolute form.
 int setupTube(int N, int D, int r, int S, int K, const uint8_t* mask,
               const double* vals, const double* times_cp, const double* times,
-              const double* radii, TubeProblem* tp) {
+              const double* radii, TubeProblem* tp, bool relative = true) {
   if (!mask || !vals || !times || !times_cp || !radii || S < 1) return -1;
+  tp->origin.assign(D, 0.0);
+  std::vector<double> rel(vals, vals + static_cast<size_t>(S + 1) * K * D);
+  if (relative && mask[0] && mask[S * K]) {
+    const double* last = vals + static_cast<size_t>(S) * K * D;
+    for (int d = 0; d < D; ++d) tp->origin[d] = 0.5 * (vals[d] + last[d]);
+    for (int v = 0; v <= S; ++v)
+      if (mask[v * K])
+        for (int d = 0; d < D; ++d) rel[static_cast<size_t>(v) * K * D + d] -= tp->origin[d];
+  }
+  vals = rel.data();
   tp->lp.N = N;
   tp->lp.D = D;
   tp->radii.clear();
@@ -1802,7 +1834,7 @@ int orc_tube_qcqp_assemble(int N, int D, int r, int S, int K,
                            const double* radii, double* P, double* q,
                            double* quad, double* lin, double* cst, int* n_free) {
   TubeProblem tp;
-  int rc = setupTube(N, D, r, S, K, mask, vals, times_cp, times, radii, &tp);
+  int rc = setupTube(N, D, r, S, K, mask, vals, times_cp, times, radii, &tp, false);
   if (rc) return rc;
   const int n = tp.npk;
   if (n_free) *n_free = n;
@@ -1840,6 +1872,7 @@ int orc_tube_residuals(int N, int D, int r, int S, int K, const uint8_t* mask,
   int rc = setupTube(N, D, r, S, K, mask, vals, times_cp, times, radii, &tp);
   if (rc) return rc;
   std::vector<double> xv(x, x + tp.npk);
+  tp.shiftPositions(&xv, -1.0);
   for (size_t k = 0; k < tp.cons.size(); ++k) resid[k] = tp.residual(tp.cons[k], xv);
   return 0;
 }
@@ -1871,9 +1904,15 @@ static int tubeQcqpSolve(int N, int D, int r, int S, int K, const uint8_t* mask,
   if (status < 0) return status;
   if (status == 2) status = -22;  // numerical breakdown away from the optimum
   tp.recover(x);
+  // The cost is that of the relative problem (a translation does not change
+  // it); x and the constant coefficients go back to world coordinates.
+  if (cost) *cost = tp.lp.computeCost();
+  tp.shiftPositions(&x, 1.0);
+  for (int s = 0; s < S; ++s)
+    for (int d = 0; d < D; ++d)
+      tp.lp.coeffs[(static_cast<size_t>(s) * D + d) * N] += tp.origin[d];
   if (x_out) std::memcpy(x_out, x.data(), sizeof(double) * x.size());
   if (coeffs) std::memcpy(coeffs, tp.lp.coeffs.data(), sizeof(double) * tp.lp.coeffs.size());
-  if (cost) *cost = tp.lp.computeCost();
   if (iters) *iters = it;
   return status;
 }
