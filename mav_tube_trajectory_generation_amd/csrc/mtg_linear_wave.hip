@@ -22,6 +22,11 @@ namespace wave {
 #endif
 constexpr int kWpb = MTG_WAVE_WPB;
 static_assert(kWpb >= 1 && kWpb <= 4, "1 to 4 waves per workgroup");
+// A/B builds of round 7 (5.1.1a): -DMTG_WAVE_T_DIRECT=0 hands the assembly
+// lanes their segment times through LDS like every other input.
+#ifndef MTG_WAVE_T_DIRECT
+#define MTG_WAVE_T_DIRECT 1
+#endif
 
 // The problem count nb is an argument in the first 64 bytes (the first 56
 // are preloaded into SGPRs; nb is the one scalar load before the first
@@ -68,6 +73,14 @@ __global__ __launch_bounds__(kWave * kWpb) void linear_wave_kernel(
   double f1 = 0.0;
   if constexpr (D * NFIX > kWave) f1 = fb[lane + kWave < D * NFIX ? lane + kWave : D * NFIX - 1];
   const double t_own = tb[lane < S ? lane : S - 1];
+  // The assembly's chain starts at its lanes' two times (T -> 1/T -> powers):
+  // those come straight from memory (the same cache line as t_own), not
+  // through the LDS copy the later phases use.
+  [[maybe_unused]] double tl = 0.0, tr = 0.0;
+  if constexpr (MTG_WAVE_T_DIRECT) {
+    tl = tb[sv.tl_index()];
+    tr = tb[sv.av];
+  }
   const double2 h_own = *reinterpret_cast<const double2*>(tab + 2 * (lane < N * N / 2 ? lane : 0));
   double* T = sv.aux();
   sv.store_constants(f0, f1, h_own);
@@ -85,7 +98,7 @@ __global__ __launch_bounds__(kWave * kWpb) void linear_wave_kernel(
     if (status && lane == 0) status[b] = MTG_TRAJ_BAD_TIME;
     return;
   }
-  const bool not_spd = sv.solve(T);
+  const bool not_spd = MTG_WAVE_T_DIRECT ? sv.solve(T, tl, tr) : sv.solve(T);
   // The coefficients are staged in the chain slots (free after solve()) and
   // copied out with consecutive lanes on consecutive 16-byte pieces: three
   // stores over 19 cache lines instead of five over 95 (lane (s, d) writes

@@ -14,8 +14,8 @@
 //     backward chain's v = S-1 .. MID+1 sit in the slots (chain, step) in
 //     elimination order, each slot holding the vertex's Schur block (packed
 //     lower triangle), the step's coupling P^T by rows, the right-hand sides
-//     (then z) and Z by rows; slot (0, MID-1) is the middle vertex, slot
-//     (1, NB) receives the backward chain's terms;
+//     (then z) and Z by rows; slot (0, MID-1) is the middle vertex, stored
+//     once with both chains' terms (added in registers);
 //   * a step runs on lanes (chain, column j, row i): column lanes j < 4 solve
 //     for column j of the coupling, right-hand-side lanes j = 4 + d for
 //     dimension d, and each lane of the four rows i forms only row i of its
@@ -30,6 +30,16 @@
 #include <stdint.h>
 
 #include "mtg_std_device.h"
+
+// A/B builds of the two changes of round 7 around the sweep (5.1.1a):
+// -DMTG_WAVE_END_IN_PASS=0 keeps the end-vertex terms a pass of their own at
+// every S, -DMTG_WAVE_MID_REG=0 the backward chain's terminal slot.
+#ifndef MTG_WAVE_END_IN_PASS
+#define MTG_WAVE_END_IN_PASS 1
+#endif
+#ifndef MTG_WAVE_MID_REG
+#define MTG_WAVE_MID_REG 1
+#endif
 
 namespace mtg {
 namespace wave {
@@ -57,11 +67,16 @@ struct Geo {
   static constexpr int O_R = O_P + MF * MF;        // right-hand sides, then z (D x MF)
   static constexpr int O_Z = O_R + D * MF;         // Z = S^-1 P by rows (MF x MF)
   static constexpr int SLOT = O_Z + MF * MF;
+  // The 2 D MF end-term lanes (e, d, i) ride in the assembly pass behind the
+  // row lanes when the wave has room for both (S <= 11 at MF = 4, D = 3);
+  // their row stores go to a junk slot.
+  static constexpr bool kEndInPass = MTG_WAVE_END_IN_PASS && NROW + 2 * D * MF <= kWave;
+  static constexpr int NJUNK = kEndInPass ? SLOT : 16;
   // LDS carve-up (doubles).
   static constexpr int L_DV = 0;                          // (S+1) x D x MP vertex derivatives
   static constexpr int L_SL = L_DV + (S + 1) * D * MP;    // 2 x NSL slots
   static constexpr int L_JUNK = L_SL + 2 * NSL * SLOT;    // stores nobody reads
-  static constexpr int L_H = L_JUNK + 16;                 // H(1), N x N
+  static constexpr int L_H = L_JUNK + NJUNK;              // H(1), N x N
   static constexpr int L_AUX = L_H + N * N;               // times and optimiser state
   static constexpr int NAUX = (6 * S + 8 + 1) & ~1;
   static constexpr int L_N = L_AUX + NAUX;
@@ -128,6 +143,15 @@ __device__ inline void lds_st(double* p, const double (&v)[K]) {
   if (K & 1) p[K - 1] = v[K - 1];
 }
 
+// The value of lane 32 + (l & 31) in every lane l (VALU, no LDS).
+__device__ inline double upper_half(double x) {
+  const long long u = __builtin_bit_cast(long long, x);
+  const unsigned lo = static_cast<unsigned>(u), hi = static_cast<unsigned>(u >> 32);
+  const auto a = __builtin_amdgcn_permlane32_swap(lo, lo, false, false);
+  const auto b = __builtin_amdgcn_permlane32_swap(hi, hi, false, false);
+  return stdp::join64(static_cast<int>(a[1]), static_cast<int>(b[1]));
+}
+
 // Compiler-only memory fence: LDS operations of one wavefront complete in
 // issue order, so a value another lane stored is visible to every later
 // load; this keeps the compiler from moving a load above such a store.
@@ -144,9 +168,13 @@ struct Solver {
   int lane;
   // Lane roles: assembly row (av, ai) (lanes past the last row repeat vertex
   // S-1's rows, same row i = lane % MF, which the end-term lanes also use),
-  // coefficient lane (cs, cd), end-term lane (ee, ed), sweep lane (g, jj, ii).
+  // coefficient lane (cs, cd), end-term lane (ee, ed) (endl: the lanes
+  // NROW .. NROW + 2 D MF - 1 with kEndInPass, else 0 .. 2 D MF - 1), sweep
+  // lane (g, jj, ii).
+  static constexpr bool kEndInPass = G::kEndInPass;
+  static constexpr bool kMidReg = MTG_WAVE_MID_REG;
   int ai, av, cs, cd, ee, ed, g, q, jj, ii;
-  bool i1, i2, i3;
+  bool i1, i2, i3, endl;
 
   __device__ void init(double* smem) {
     sm = smem;
@@ -160,8 +188,11 @@ struct Solver {
     const int sd = lane < S * D ? lane : S * D - 1;
     cs = sd / D;
     cd = sd - cs * D;
-    ee = (lane / (D * MF)) & 1;
-    ed = (lane / MF) % D;
+    // NROW is a multiple of MF, so an end lane's row is ai as well
+    const int el = kEndInPass ? (lane >= G::NROW ? lane - G::NROW : 0) : lane;
+    ee = (el / (D * MF)) & 1;
+    ed = (el / MF) % D;
+    endl = (!kEndInPass || lane >= G::NROW) && el < 2 * D * MF;
     g = lane >> 5;
     q = lane & 31;
     jj = q >> 2;
@@ -207,10 +238,18 @@ struct Solver {
   // A solve at the segment times T (LDS, S valid values): dv receives every
   // vertex derivative.  Returns true if a pivot was not positive
   // (wave-uniform).  All lanes call.
-  __device__ bool solve(const double* T) {
+  __device__ bool solve(const double* T) { return solve(T, T[tl_index()], T[av]); }
+  // The segment whose time is the assembly lane's left time: segment av - 1
+  // for a row lane, the end segment for an end lane of the same pass.
+  __device__ int tl_index() const {
+    return kEndInPass && endl ? (ee ? S - 1 : 0) : av - 1;
+  }
+  // The same with the lane's times T[tl_index()] and T[av] given (a caller
+  // that has them from memory spares the assembly the LDS hop).
+  __device__ bool solve(const double* T, double tl, double tr) {
     // With no backward step (S = 2) the middle vertex reads the backward
     // chain's terminal slot as zero; otherwise its last step writes it.
-    if constexpr (NBW == 0) {
+    if constexpr (NBW == 0 && !kMidReg) {
       double* term = slots + NSL * SLOT;
       if (lane < G::TRI) term[O_S + lane] = 0.0;
       if (lane < D * MF) term[O_R + lane] = 0.0;
@@ -218,10 +257,32 @@ struct Solver {
     // ---- assembly.  Lane (v, i): row i (derivative k = i+1) of A_v =
     // H11(v-1) + H00(v), of C_v = H01(v) and b_v = -R_pf d_f on that row.
     // Exponent of H(a, b) at T: 1 - 2r + (a mod M) + (b mod M).
-    const double tl = T[av - 1], tr = T[av], te = T[ee ? S - 1 : 0];
-    double hk[N], hMk[N];
+    // With kEndInPass the end lane (e, d, i) runs the same instructions on
+    // its segment's time as the left time and on the four H(1) entries of
+    // its end term in place of the row lane's H11 entries (hx: a per-lane
+    // LDS address), so its products hx[j] ql[j+1] are the end term's.
+    const bool endp = kEndInPass && endl;
+    double hk[N], hx[MF], he0[MF], hM0, hMM;
     lds_ld(hh + (ai + 1) * N, hk);
-    lds_ld(hh + (M + ai + 1) * N, hMk);
+    if constexpr (kEndInPass) {
+      const double* hm = hh + (M + ai + 1) * N;
+      hM0 = hm[0];
+      hMM = hm[M];
+      // e = 0 starts at column 1: 8-byte aligned only, so single doubles
+      const double* px = endp ? (ee ? hh + (ai + 1) * N + M + 1 : hm + 1) : hm + M + 1;
+#pragma unroll
+      for (int j = 0; j < MF; ++j) hx[j] = px[j];
+    } else {
+      double hMk[N];
+      lds_ld(hh + (M + ai + 1) * N, hMk);
+      hM0 = hMk[0];
+      hMM = hMk[M];
+#pragma unroll
+      for (int j = 0; j < MF; ++j) {
+        hx[j] = hMk[M + j + 1];
+        he0[j] = hMk[j + 1];
+      }
+    }
     double pos[3][D], endd[M - 1];
 #pragma unroll
     for (int w = 0; w < 3; ++w)
@@ -239,17 +300,19 @@ struct Solver {
       double ql[M], qr[M];
       row_powers<M, R>(tl, i1, i2, i3, ql);
       row_powers<M, R>(tr, i1, i2, i3, qr);
-      double Ar[MF], Cr[MF];
+      double Ar[MF], Cr[MF], s_end = 0.0;
 #pragma unroll
       for (int j = 0; j < MF; ++j) {
-        Ar[j] = fma(hMk[M + j + 1], ql[j + 1], hk[j + 1] * qr[j + 1]);
+        Ar[j] = fma(hx[j], ql[j + 1], hk[j + 1] * qr[j + 1]);
         Cr[j] = hk[M + j + 1] * qr[j + 1];
+        // (the rounded product, as the separate pass forms it: the same bits)
+        if constexpr (kEndInPass) s_end = fma(hx[j] * ql[j + 1], endd[j], s_end);
       }
-      const double cpos = fma(hMk[M], ql[0], hk[0] * qr[0]);  // p_v
-      const double cprev = hMk[0] * ql[0];                     // p_{v-1}
-      const double cnext = hk[M] * qr[0];                      // p_{v+1}
+      const double cpos = fma(hMM, ql[0], hk[0] * qr[0]);  // p_v
+      const double cprev = hM0 * ql[0];                     // p_{v-1}
+      const double cnext = hk[M] * qr[0];                   // p_{v+1}
       MTG_STAMP(1);
-      double* sl = slot_of(av);
+      double* sl = endp ? junk : slot_of(av);
 #ifndef MTG_ABL_NOB  // diagnostic ablation builds only (tools/gpu_r05_abl.sh)
 #pragma unroll
       for (int d = 0; d < D; ++d) {
@@ -277,22 +340,28 @@ struct Solver {
 #pragma unroll
       for (int j = 0; j < MF; ++j) pc[j * ps] = Cr[j];
 #endif
-    }
-    lds_order();
-    MTG_STAMP(12);
-    // The fully fixed end vertices' part of b_1 (segment 0) and b_(S-1)
-    // (segment S-1): lane (e, d, i) adds -sum_l H_seg(k, l) d_f(l) for its row.
+      lds_order();
+      MTG_STAMP(12);
+      // The fully fixed end vertices' part of b_1 (segment 0) and b_(S-1)
+      // (segment S-1): lane (e, d, i) adds -sum_l H_seg(k, l) d_f(l) for its
+      // row, after the row lanes' stores of b (LDS operations of a wave
+      // complete in issue order).
 #ifndef MTG_ABL_NOEND
-    {
-      double qe[M];
-      row_powers<M, R>(te, i1, i2, i3, qe);
-      double s = 0.0;
+      if constexpr (kEndInPass) {
+        if (endp) atomicAdd(slot_of(ee ? S - 1 : 1) + O_R + ed * MF + ai, -s_end);
+      } else {
+        // a pass of its own on the lanes 0 .. 2 D MF - 1 (S >= 12: the row
+        // lanes leave no room)
+        double qe[M];
+        row_powers<M, R>(T[ee ? S - 1 : 0], i1, i2, i3, qe);
+        double s = 0.0;
 #pragma unroll
-      for (int l = 1; l < M; ++l) s = fma((ee ? hk[M + l] : hMk[l]) * qe[l], endd[l - 1], s);
-      // lanes past the 2 D MF end lanes repeat one and add nothing
-      atomicAdd(slot_of(ee ? S - 1 : 1) + O_R + ed * MF + ai, lane < 2 * D * MF ? -s : 0.0);
-    }
+        for (int l = 1; l < M; ++l) s = fma((ee ? hk[M + l] : he0[l - 1]) * qe[l], endd[l - 1], s);
+        // lanes past the 2 D MF end lanes repeat one and add nothing
+        atomicAdd(slot_of(ee ? S - 1 : 1) + O_R + ed * MF + ai, endl ? -s : 0.0);
+      }
 #endif
+    }
     lds_order();
     MTG_STAMP(2);
 
@@ -326,6 +395,15 @@ struct Solver {
         double pc[MF], a;
         lds_ld(Pp, pc);
         a = Ap[0];
+        // kMidReg: the two chains' last outputs (A_m - forward terms, 0 -
+        // backward terms) are added in registers (the backward half's value
+        // comes to the forward half's lane by v_permlane32_swap) and the
+        // middle slot (0, NFW) is stored once.  With NFW < NBW (odd S) the
+        // forward chain ends a step earlier: its lanes keep their last output
+        // (of; at NFW = 0 the assembly's A_m entry) until the backward chain's
+        // last step (ol).
+        [[maybe_unused]] double of = 0.0, ol = 0.0;
+        if constexpr (kMidReg && NFW == 0) of = Ap[-SLOT];
 #pragma unroll
         for (int k = 0; k < NK; ++k) {
           MTG_STAMP(100 + 2 * k);
@@ -346,9 +424,8 @@ struct Solver {
               an = Ap[(k + 1) * SLOT];
             }
             block2_solve(Sv, u, x, pmin);
-            // The backward chain's last step stores 0 - P^T x into its
-            // terminal slot (the backward terms of the middle vertex): a is
-            // 0 there instead of a zeroed slot's entry (no zeroing stores).
+            // The backward chain's last step forms 0 - P^T x (the backward
+            // terms of the middle vertex): a is 0 there.
             if (k == NBW - 1) a = g ? 0.0 : a;
             // block2_solve finishes x[2], x[3] first
             double o = fma(-pc[2], x[2], a);
@@ -360,12 +437,26 @@ struct Solver {
             xi = i2 ? x[2] : xi;
             xi = i3 ? x[3] : xi;
             Xp[k * SLOT] = xi;
-            Op[k * SLOT] = o;
+            if (kMidReg && k == NBW - 1) {
+              // (the backward half's lanes store a sum nobody reads)
+              if constexpr (NFW == NBW) Op[k * SLOT] = o + upper_half(o);
+              ol = o;
+            } else {
+              Op[k * SLOT] = o;
+              if (kMidReg && NFW < NBW && k == NFW - 1) of = o;
+            }
             lds_order();
             if (k + 1 < NK) {
 #pragma unroll
               for (int m = 0; m < MF; ++m) pc[m] = pcn[m];
               a = an;
+            }
+          }
+          if constexpr (kMidReg && NFW < NBW) {
+            if (k == NBW - 1) {  // all lanes again: the exchange reads both halves
+              const double sum = of + upper_half(ol);
+              if (g == 0) Op[(NFW - 1) * SLOT] = sum;
+              lds_order();
             }
           }
         }
@@ -380,11 +471,20 @@ struct Solver {
     {
       const int d = jj;  // q = 4 d + i
       const bool p_act = q < 4 * D;
-      const double* mf = slots + NFW * SLOT;          // slot (0, NFW): A_m - forward terms
-      const double* mb = slots + (NSL + NBW) * SLOT;  // slot (1, NBW): -backward terms
+      // slot (0, NFW): A_m - forward terms (kMidReg: - backward terms too)
+      const double* mf = slots + NFW * SLOT;
       double Sv[MF][MF], rr[MF], x[MF];
       const int dc = p_act ? d : 0;
-      {
+      if constexpr (kMidReg) {
+        double t0[G::TRI];
+        lds_ld(mf + O_S, t0);
+#pragma unroll
+        for (int r = 0; r < MF; ++r)
+#pragma unroll
+          for (int c = 0; c <= r; ++c) Sv[r][c] = t0[tri(r, c)];
+        lds_ld(mf + O_R + dc * MF, rr);
+      } else {
+        const double* mb = slots + (NSL + NBW) * SLOT;  // slot (1, NBW): -backward terms
         double t0[G::TRI], t1[G::TRI];
         lds_ld(mf + O_S, t0);
         lds_ld(mb + O_S, t1);
