@@ -27,6 +27,7 @@
 #include "mtg_free_device.h"
 #include "mtg_internal.h"
 #include "mtg_sbplx_device.h"
+#include "mtg_time_device.h"  // fd_time
 
 namespace mtg {
 
@@ -372,8 +373,7 @@ __global__ __launch_bounds__(kWave) void time_free_optimize_kernel(
         const int nn = gi >> 1;
         for (int i = t.lane; i < S; i += kWave) {
           const double Tn = Tcur[i];
-          Ttry[i] = i != nn ? Tn
-                            : (Tn <= 0.1 ? 0.1 : ((gi & 1) ? Tn + p.increment : Tn - p.increment));
+          Ttry[i] = i != nn ? Tn : fd_time(Tn, gi, p.increment);
         }
         __syncthreads();
         set_point(Ttry, dcur);
@@ -485,33 +485,15 @@ __global__ __launch_bounds__(kWave) void time_free_sbplx_kernel(
 }
 
 namespace {
-template <typename K>
-hipError_t prepare_lds_free(K kernel, size_t bytes) {
-  if (bytes > 65536)
-    return hipFuncSetAttribute(reinterpret_cast<const void*>(kernel),
-                               hipFuncAttributeMaxDynamicSharedMemorySize,
-                               static_cast<int>(bytes));
-  return hipSuccess;
-}
-
 template <int N>
 hipError_t free_cost_n(const PlanDev& pl, int64_t B, const double* df, const double* dp,
                        const double* times, const mtg_time_params& p, int mode, double* cost,
                        double* grad, int32_t* status, hipStream_t st) {
-  const bool soft = p.n_soft > 0;
-  const size_t bytes = free_lds(N, pl.S, pl.D, pl.np, soft).bytes;
-  if (soft) {
-    hipError_t e = prepare_lds_free(free_cost_kernel<N, true>, bytes);
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL((free_cost_kernel<N, true>), dim3(static_cast<unsigned>(B)), dim3(kWave),
-                       bytes, st, pl, df, dp, times, p, mode, cost, grad, status);
-  } else {
-    hipError_t e = prepare_lds_free(free_cost_kernel<N, false>, bytes);
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL((free_cost_kernel<N, false>), dim3(static_cast<unsigned>(B)),
-                       dim3(kWave), bytes, st, pl, df, dp, times, p, mode, cost, grad, status);
-  }
-  return hipGetLastError();
+  return with_soft(p.n_soft > 0, [&](auto soft) {
+    return launch(free_cost_kernel<N, decltype(soft)::value>, B, kWave,
+                  free_lds(N, pl.S, pl.D, pl.np, soft).bytes, st, pl, df, dp, times, p, mode, cost,
+                  grad, status);
+  });
 }
 
 template <int N>
@@ -519,22 +501,11 @@ hipError_t free_opt_n(const PlanDev& pl, int64_t B, const double* df, double* dp
                       const double* times, const double* lower, const double* upper,
                       const mtg_time_params& p, int max_evals, double* cost, int32_t* evals,
                       int32_t* status, hipStream_t st) {
-  const bool soft = p.n_soft > 0;
-  const size_t bytes = free_lds(N, pl.S, pl.D, pl.np, soft).bytes;
-  if (soft) {
-    hipError_t e = prepare_lds_free(free_optimize_kernel<N, true>, bytes);
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL((free_optimize_kernel<N, true>), dim3(static_cast<unsigned>(B)),
-                       dim3(kWave), bytes, st, pl, df, dp, times, lower, upper, p, max_evals,
-                       cost, evals, status);
-  } else {
-    hipError_t e = prepare_lds_free(free_optimize_kernel<N, false>, bytes);
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL((free_optimize_kernel<N, false>), dim3(static_cast<unsigned>(B)),
-                       dim3(kWave), bytes, st, pl, df, dp, times, lower, upper, p, max_evals,
-                       cost, evals, status);
-  }
-  return hipGetLastError();
+  return with_soft(p.n_soft > 0, [&](auto soft) {
+    return launch(free_optimize_kernel<N, decltype(soft)::value>, B, kWave,
+                  free_lds(N, pl.S, pl.D, pl.np, soft).bytes, st, pl, df, dp, times, lower, upper,
+                  p, max_evals, cost, evals, status);
+  });
 }
 }  // namespace
 
@@ -542,22 +513,11 @@ template <int N>
 hipError_t time_free_opt_n(const PlanDev& pl, int64_t B, const double* df, double* dp,
                            double* times, const mtg_time_params& p, int max_evals, double* cost,
                            int32_t* evals, int32_t* status, hipStream_t st) {
-  const bool soft = p.n_soft > 0;
-  const size_t bytes = free_lds(N, pl.S, pl.D, pl.np, soft).bytes;
-  if (soft) {
-    hipError_t e = prepare_lds_free(time_free_optimize_kernel<N, true>, bytes);
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL((time_free_optimize_kernel<N, true>), dim3(static_cast<unsigned>(B)),
-                       dim3(kWave), bytes, st, pl, df, dp, times, p, max_evals, cost, evals,
-                       status);
-  } else {
-    hipError_t e = prepare_lds_free(time_free_optimize_kernel<N, false>, bytes);
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL((time_free_optimize_kernel<N, false>), dim3(static_cast<unsigned>(B)),
-                       dim3(kWave), bytes, st, pl, df, dp, times, p, max_evals, cost, evals,
-                       status);
-  }
-  return hipGetLastError();
+  return with_soft(p.n_soft > 0, [&](auto soft) {
+    return launch(time_free_optimize_kernel<N, decltype(soft)::value>, B, kWave,
+                  free_lds(N, pl.S, pl.D, pl.np, soft).bytes, st, pl, df, dp, times, p, max_evals,
+                  cost, evals, status);
+  });
 }
 
 size_t free_lds_bytes(int N, int S, int D, int np, bool soft) {
@@ -572,22 +532,11 @@ hipError_t time_free_sbplx_n(const PlanDev& pl, int64_t B, const double* df, dou
                              double* times, const mtg_time_params& p, int max_evals,
                              double* cost, int32_t* evals, int32_t* result, int32_t* status,
                              hipStream_t st) {
-  const bool soft = p.n_soft > 0;
-  const size_t bytes = free_sbplx_lds(N, pl.S, pl.D, pl.np, soft).bytes;
-  if (soft) {
-    hipError_t e = prepare_lds_free(time_free_sbplx_kernel<N, true>, bytes);
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL((time_free_sbplx_kernel<N, true>), dim3(static_cast<unsigned>(B)),
-                       dim3(kWave), bytes, st, pl, df, dp, times, p, max_evals, cost, evals,
-                       result, status);
-  } else {
-    hipError_t e = prepare_lds_free(time_free_sbplx_kernel<N, false>, bytes);
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL((time_free_sbplx_kernel<N, false>), dim3(static_cast<unsigned>(B)),
-                       dim3(kWave), bytes, st, pl, df, dp, times, p, max_evals, cost, evals,
-                       result, status);
-  }
-  return hipGetLastError();
+  return with_soft(p.n_soft > 0, [&](auto soft) {
+    return launch(time_free_sbplx_kernel<N, decltype(soft)::value>, B, kWave,
+                  free_sbplx_lds(N, pl.S, pl.D, pl.np, soft).bytes, st, pl, df, dp, times, p,
+                  max_evals, cost, evals, result, status);
+  });
 }
 
 #define MTG_FREE_DISPATCH(FN, ...)        \

@@ -1,9 +1,12 @@
 // mtg_internal.h — shared between the host ABI (mtg_host.cpp) and the kernel
-// launchers (mtg_kernels.hip, mtg_tube.hip).  Not part of the public ABI.
+// launchers (mtg_kernels.hip, mtg_tube.hip), with the launch helpers the
+// launchers share.  Not part of the public ABI.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stddef.h>
 #include <stdint.h>
+
+#include <type_traits>
 
 #include "../../include/mtg_hip.h"
 
@@ -195,6 +198,33 @@ int tube_time_optimize(const TubeArgs& a, double* times_io, double tol, int max_
                        hipStream_t st);
 
 constexpr int kMaxLdsBytes = 160 * 1024;
+
+// Launch helpers of the one-workgroup-per-problem kernels.
+// Dynamic LDS beyond the 64 KiB default needs the kernel's limit raised.
+template <typename K>
+hipError_t prepare_lds(K kernel, size_t bytes) {
+  if (bytes > 65536)
+    return hipFuncSetAttribute(reinterpret_cast<const void*>(kernel),
+                               hipFuncAttributeMaxDynamicSharedMemorySize,
+                               static_cast<int>(bytes));
+  return hipSuccess;
+}
+// prepare_lds, launch `grid` workgroups of `threads`, hipGetLastError.
+template <typename... P, typename... A>
+hipError_t launch(void (*kernel)(P...), int64_t grid, int threads, size_t lds_bytes,
+                  hipStream_t st, A... args) {
+  const hipError_t e = prepare_lds(kernel, lds_bytes);
+  if (e != hipSuccess) return e;
+  hipLaunchKernelGGL(kernel, dim3(static_cast<unsigned>(grid)), dim3(threads), lds_bytes, st,
+                     args...);
+  return hipGetLastError();
+}
+// f(std::true_type) or f(std::false_type) by `soft`: the launchers of the
+// kernels templated on kSoft name K<..., decltype(soft)::value> once.
+template <typename F>
+hipError_t with_soft(bool soft, F f) {
+  return soft ? f(std::true_type{}) : f(std::false_type{});
+}
 
 // Trajectory sampling (mtg_sample.hip).
 constexpr int kMaxSampleS = 64;  // segments staged in LDS per trajectory

@@ -1,6 +1,8 @@
 // mtg_kernels.hip — gfx950 kernels of the linear-solve and time-allocation
 // hot path.  One 64-lane workgroup per trajectory; all per-trajectory state in
-// LDS (mtg_device.h).  Launchers at the bottom are called by mtg_host.cpp.
+// LDS (mtg_device.h).  The time kernels are the generic solver's objective
+// (objective_at) under the shared cost driver and optimiser of
+// mtg_time_device.h.  Launchers at the bottom are called by mtg_host.cpp.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -9,6 +11,7 @@
 #include "mtg_extrema_device.h"
 #include "mtg_internal.h"
 #include "mtg_sbplx_device.h"
+#include "mtg_time_device.h"
 
 namespace mtg {
 
@@ -205,40 +208,43 @@ __host__ __device__ inline size_t sbplx_state_offset(const Layout& lay, int S, i
   return (end + 15) / 16 * 16;
 }
 
-// The reference's getCostAndGradientTime (grad_mode 1): with d held at the
-// base solution (dv), J_d(T') differs from J_d(T) only in segment n's block
-// (nonlinear_impl:2495-2584).  No re-solve.  Gradient written to g (LDS).
-template <int N>
-__device__ void gradient_fixed_d(Traj<N>& t, const mtg_time_params& p, double* g) {
-  const double inc = p.increment;
-  for (int n = 0; n < t.S; ++n) {
-    const double Tn = t.T()[n];
-    const double ts = Tn <= 0.1 ? 0.1 : Tn - inc;  // nonlinear_impl:2529-2530
-    const double tb = Tn <= 0.1 ? 0.1 : Tn + inc;
-    const double qs = t.seg_energy_at(n, ts);
-    const double qb = t.seg_energy_at(n, tb);
-    if (t.lane == 0) g[n] = p.w_d * (qb - qs) / (2.0 * inc) + p.w_t * 1.0;
+// The evaluator of the shared drivers (mtg_time_device.h): Traj<N> with the
+// drivers' hooks.  The evaluation point is the solver's T(), the drivers'
+// state the layout's aux region, the flags the solver's (compute_powers and
+// solve set them, nothing clears them).
+template <int N, bool kSoft>
+struct TrajEval : Traj<N> {
+  __device__ __attribute__((always_inline)) double* state(int) const {
+    return this->sm + this->lay->aux;
   }
-  __syncthreads();
-}
-
-// Central-difference point of gradient step gi (0 .. 2S-1) around base
-// times Tb: segment n = gi / 2 at T_n - inc (even gi) or T_n + inc (odd),
-// both clamped to 0.1 when T_n <= 0.1 (nonlinear_impl:2529-2530).
-template <int N>
-__device__ void set_fd_point(Traj<N>& t, const double* Tb, int gi, double inc) {
-  const int n = gi >> 1;
-  if (t.lane == 0) {
-    for (int i = 0; i < t.S; ++i) t.T()[i] = Tb[i];
-    const double Tn = Tb[n];
-    t.T()[n] = Tn <= 0.1 ? 0.1 : ((gi & 1) ? Tn + inc : Tn - inc);
+  __device__ __attribute__((always_inline)) double eval(int, const double* __restrict__ tab,
+                                                        double* cbuf, const mtg_time_params& p,
+                                                        double* viol) {
+    return objective_at<N, kSoft>(*this, tab, p, cbuf, viol);
   }
-  __syncthreads();
-}
+  __device__ __attribute__((always_inline)) bool bad() const {
+    return (this->flag()[0] & 1) != 0;
+  }
+  __device__ __attribute__((always_inline)) bool not_spd() const {
+    return (this->flag()[0] & 2) != 0;
+  }
+  // The reference's getCostAndGradientTime: with d held at the base solution
+  // (dv), J_d(T') differs from J_d(T) only in segment n's block
+  // (nonlinear_impl:2495-2584).  No re-solve; the wave sums each energy.
+  __device__ __attribute__((always_inline)) void fixed_d_gradient(
+      int S, const double* Tb, const mtg_time_params& p, double* g, double* /*scratch*/) {
+    const double inc = p.increment;
+    for (int n = 0; n < S; ++n) {
+      const double qs = this->seg_energy_at(n, fd_time(Tb[n], 0, inc));
+      const double qb = this->seg_energy_at(n, fd_time(Tb[n], 1, inc));
+      if (this->lane == 0) g[n] = p.w_d * (qb - qs) / (2.0 * inc) + p.w_t * 1.0;
+    }
+    __syncthreads();
+  }
+};
 
-// Every objective evaluation of the two kernels below goes through ONE call
-// site of objective_at (a loop over evaluation points), so the solver body
-// is instantiated once per kernel and stays within the register file.
+// objectiveFunctionTime / getCostAndGradientTime and optimizeTime on the
+// generic solver: the drivers of mtg_time_device.h around objective_at.
 template <int N, bool kSoft>
 __global__ __launch_bounds__(kWave) void time_cost_kernel(
     PlanDev pl, const double* __restrict__ fixed_vals, const double* __restrict__ times,
@@ -246,54 +252,15 @@ __global__ __launch_bounds__(kWave) void time_cost_kernel(
     int32_t* __restrict__ status) {
   extern __shared__ __attribute__((aligned(16))) double smem[];
   const int S = pl.S, D = pl.D, nf = pl.nf;
-  const double* tab = pl.tab;
   const Layout lay = make_layout(N, S, D);
-  Traj<N> t{S, D, pl.r, &lay, smem, reinterpret_cast<int*>(smem + lay.ndouble),
-            static_cast<int>(threadIdx.x), pl.fmask, pl.use_mask != 0};
+  TrajEval<N, kSoft> ev{{S, D, pl.r, &lay, smem, reinterpret_cast<int*>(smem + lay.ndouble),
+                         static_cast<int>(threadIdx.x), pl.fmask, pl.use_mask != 0}};
   const int64_t b = blockIdx.x;
   double* cbuf = reinterpret_cast<double*>(reinterpret_cast<char*>(smem) + soft_cbuf_offset(lay));
-  double* g = smem + lay.aux;   // gradient
-  double* Tb = g + S;           // base times
-  t.load_inputs(pl.tab, pl.slots, pl.fixed_map, times + b * S, fixed_vals + b * D * nf, nf);
-  for (int i = t.lane; i < S; i += kWave) Tb[i] = times[b * S + i];
-  const bool fd = grad && p.grad_mode == 2;
-  const int nevals = 1 + (fd ? 2 * S : 0);
-  double J0 = 0.0, Jlo = 0.0;
-  int fl = 0;
-  for (int e = 0; e < nevals; ++e) {
-    if (e > 0) set_fd_point(t, Tb, e - 1, p.increment);
-    double viol;
-    const double J = objective_at<N, kSoft>(t, tab, p, cbuf, &viol);
-    if (e == 0) {
-      J0 = J;
-      fl = t.flag()[0];
-      if (fl & 1) break;
-    } else if ((e - 1) & 1) {
-      if (t.lane == 0) g[(e - 1) >> 1] = (J - Jlo) / (2.0 * p.increment);
-    } else {
-      Jlo = J;
-    }
-  }
-  __syncthreads();
-  if (grad && p.grad_mode == 1 && !(fl & 1)) gradient_fixed_d(t, p, g);
-  const int fl2 = t.flag()[0];
-  if (t.lane == 0) {
-    if (cost) cost[b] = (fl & 1) ? NAN : J0;
-    if (status)
-      status[b] = (fl2 & 1) ? MTG_TRAJ_BAD_TIME
-                            : ((fl2 & 2) ? MTG_TRAJ_NOT_SPD : MTG_TRAJ_OK);
-  }
-  if (grad && p.grad_mode != 0)
-    for (int i = t.lane; i < S; i += kWave) grad[b * S + i] = (fl & 1) ? NAN : g[i];
+  ev.load_inputs(pl.tab, pl.slots, pl.fixed_map, times + b * S, fixed_vals + b * D * nf, nf);
+  time_cost_drive(ev, S, pl.tab, cbuf, times, p, cost, grad, status);
 }
 
-// ---------------------------------------------------------------------------
-// Batched segment-time optimisation (optimizeTime, nonlinear_impl:332-397):
-// bounds [0.1, 2 T0]; projected, scaled steepest descent on the grad_mode 2
-// gradient with an expand/backtrack step rule; `max_evals` objective
-// evaluations (NLopt maxeval semantics, nonlinear_impl:101; gradient
-// evaluations are not counted).  Written as a state machine with one
-// objective evaluation per loop trip.
 template <int N, bool kSoft>
 __global__ __launch_bounds__(kWave) void time_optimize_kernel(
     PlanDev pl, const double* __restrict__ fixed_vals, double* __restrict__ times_io,
@@ -302,170 +269,34 @@ __global__ __launch_bounds__(kWave) void time_optimize_kernel(
     int32_t* __restrict__ result_out, int32_t* __restrict__ status) {
   extern __shared__ __attribute__((aligned(16))) double smem[];
   const int S = pl.S, D = pl.D, nf = pl.nf;
-  const double* tab = pl.tab;
   const Layout lay = make_layout(N, S, D);
-  Traj<N> t{S, D, pl.r, &lay, smem, reinterpret_cast<int*>(smem + lay.ndouble),
-            static_cast<int>(threadIdx.x), pl.fmask, pl.use_mask != 0};
+  TrajEval<N, kSoft> ev{{S, D, pl.r, &lay, smem, reinterpret_cast<int*>(smem + lay.ndouble),
+                         static_cast<int>(threadIdx.x), pl.fmask, pl.use_mask != 0}};
   const int64_t b = blockIdx.x;
   double* cbuf = reinterpret_cast<double*>(reinterpret_cast<char*>(smem) + soft_cbuf_offset(lay));
-  double* Tcur = smem + lay.aux;   // accepted times
-  double* T0 = Tcur + S;           // initial times (bounds)
-  double* g = T0 + S;              // gradient at Tcur
-  double* gv = g + S;              // gradient of the violation (hard constraints)
-  t.load_inputs(pl.tab, pl.slots, pl.fixed_map, times_io + b * S, fixed_vals + b * D * nf, nf);
-  for (int i = t.lane; i < S; i += kWave) {
-    const double v = times_io[b * S + i];
-    Tcur[i] = v;
-    T0[i] = v;
-  }
-  constexpr double kLower = 0.1;  // kOptimizationTimeLowerBound (:370)
-  enum { kBase, kGrad, kTrial, kDone };
-  int phase = kBase, gi = 0, evals = 0, nsolve = 0, res = 0;
-  double f = 0.0, fv = 0.0, Jlo = 0.0, vlo = 0.0;
-  double alpha = 0.1;  // initial_stepsize_rel (polynomial_optimization_nonlinear.h:55)
-  int fl = 0;
-  // LN_SBPLX (optimizer 1): the machine picks every point, lane 0 advances it
-  const bool sb = p.optimizer == 1;
   auto* sbs = reinterpret_cast<sbplx::State*>(reinterpret_cast<char*>(smem) +
                                               sbplx_state_offset(lay, S, D, N, kSoft));
-  sbplx::Machine mach{sbs};
-  if (sb) {
-    __syncthreads();
-    if (t.lane == 0)
-      mach.init(S, t.T(), p.initial_stepsize_rel > 0.0 ? p.initial_stepsize_rel : 0.1,
-                max_evals, p.f_rel, p.f_abs);
-    __syncthreads();
-    if (sbs->done) phase = kDone;  // start outside the bounds (NLopt: FAILURE)
-  }
-  while (phase != kDone) {
-    double viol;
-    const double J = objective_at<N, kSoft>(t, tab, p, cbuf, &viol);  // at T()
-    ++nsolve;
-    if (sb) {
-      if (t.flag()[0] & 1) break;
-      __syncthreads();
-      if (t.lane == 0) mach.resume(J, t.T());
-      __syncthreads();
-      if (sbs->done) break;
-      continue;
-    }
-    if (phase == kBase) {
-      f = J;
-      fv = viol;
-      evals = 1;
-      fl = t.flag()[0];
-      if (fl & 1) break;
-      phase = kGrad;
-      gi = 0;
-    } else if (phase == kGrad) {
-      if (gi & 1) {
-        if (t.lane == 0) {
-          g[gi >> 1] = (J - Jlo) / (2.0 * p.increment);
-          gv[gi >> 1] = (viol - vlo) / (2.0 * p.increment);
-        }
-      } else {
-        Jlo = J;
-        vlo = viol;
-      }
-      if (++gi == 2 * S) phase = kTrial;
-    } else {  // trial point
-      ++evals;
-      // Feasibility first (hard constraints; viol is 0 otherwise).
-      if (viol == 0.0 ? (fv > 0.0 || J < f) : viol < fv) {
-        f = J;
-        fv = viol;
-        if (t.lane == 0)
-          for (int i = 0; i < S; ++i) Tcur[i] = t.T()[i];
-        alpha = fmin(alpha * 1.5, 1.0);
-        phase = kGrad;
-        gi = 0;
-      } else {
-        alpha *= 0.5;
-      }
-    }
-    __syncthreads();
-    // Next evaluation point.
-    if (phase == kGrad) {
-      set_fd_point(t, Tcur, gi, p.increment);
-    } else if (phase == kTrial) {
-      if (!(evals < max_evals && alpha > 1e-9)) break;
-      // Scaled direction -g_n T0_n, normalised so the largest relative move
-      // is alpha; from an infeasible incumbent (hard constraints) the
-      // direction descends the violation instead.
-      const double* dir = fv > 0.0 ? gv : g;
-      double gmax = 0.0;
-      for (int i = 0; i < S; ++i) gmax = fmax(gmax, fabs(dir[i] * T0[i]));
-      if (!(gmax > 0.0)) break;
-      int moved = 0;
-      for (int i = 0; i < S; ++i) {
-        const double step = alpha * T0[i] * (dir[i] * T0[i]) / gmax;
-        double tn = Tcur[i] - step;
-        tn = fmin(fmax(tn, kLower), 2.0 * T0[i]);
-        if (tn != Tcur[i]) moved = 1;
-        if (t.lane == 0) t.T()[i] = tn;
-      }
-      __syncthreads();
-      if (!moved) break;
-    }
-  }
-  fl = t.flag()[0];
-  __syncthreads();
-  if (sb) {  // NLopt's x and opt_f: the best point and its value
-    for (int i = t.lane; i < S; i += kWave) Tcur[i] = sbplx::best_x(sbs)[i];
-    f = sbs->minf;
-    evals = sbs->nevals;
-    res = sbs->result;
-    __syncthreads();
-  } else {
-    res = evals >= max_evals ? sbplx::kMaxEval : sbplx::kXtol;
-  }
-  for (int i = t.lane; i < S; i += kWave) times_io[b * S + i] = Tcur[i];
-  if (t.lane == 0) {
-    if (cost) cost[b] = (fl & 1) ? NAN : f;
-    if (evals_out) evals_out[b] = evals;
-    if (solves_out) solves_out[b] = nsolve;
-    if (result_out) result_out[b] = res;
-    if (status)
-      status[b] = (fl & 1) ? MTG_TRAJ_BAD_TIME
-                           : ((fl & 2) ? MTG_TRAJ_NOT_SPD : MTG_TRAJ_OK);
-  }
+  ev.load_inputs(pl.tab, pl.slots, pl.fixed_map, times_io + b * S, fixed_vals + b * D * nf, nf);
+  time_optimize_drive(ev, S, pl.tab, cbuf, times_io, p, max_evals, cost, evals_out, solves_out,
+                      result_out, status, sbs);
 }
 
 // ---------------------------------------------------------------------------
 // Launchers.
-namespace {
-template <typename K>
-hipError_t prepare_lds(K kernel, size_t bytes) {
-  if (bytes > 65536)
-    return hipFuncSetAttribute(reinterpret_cast<const void*>(kernel),
-                               hipFuncAttributeMaxDynamicSharedMemorySize,
-                               static_cast<int>(bytes));
-  return hipSuccess;
-}
-}  // namespace
-
 template <int N>
 static hipError_t launch_linear_n(const PlanDev& pl, int64_t B, const double* df,
                                   const double* times, double* coeffs, double* cost,
                                   double* free_vals, int32_t* status, hipStream_t st) {
-  const size_t bytes = make_layout(N, pl.S, pl.D).bytes();
-  hipError_t e = prepare_lds(linear_solve_kernel<N>, bytes);
-  if (e != hipSuccess) return e;
-  hipLaunchKernelGGL(linear_solve_kernel<N>, dim3(static_cast<unsigned>(B)), dim3(kWave),
-                     bytes, st, pl, df, times, coeffs, cost, free_vals, status);
-  return hipGetLastError();
+  return launch(linear_solve_kernel<N>, B, kWave, make_layout(N, pl.S, pl.D).bytes(), st, pl, df,
+                times, coeffs, cost, free_vals, status);
 }
 
 template <int N>
 static hipError_t launch_coeffs_n(const PlanDev& pl, int64_t B, const double* df,
                                   const double* dp, const double* times, double* coeffs,
                                   double* cost, int32_t* status, hipStream_t st) {
-  const size_t bytes = make_layout(N, pl.S, pl.D).bytes();
-  hipError_t e = prepare_lds(coeffs_from_constraints_kernel<N>, bytes);
-  if (e != hipSuccess) return e;
-  hipLaunchKernelGGL(coeffs_from_constraints_kernel<N>, dim3(static_cast<unsigned>(B)),
-                     dim3(kWave), bytes, st, pl, df, dp, times, coeffs, cost, status);
-  return hipGetLastError();
+  return launch(coeffs_from_constraints_kernel<N>, B, kWave, make_layout(N, pl.S, pl.D).bytes(),
+                st, pl, df, dp, times, coeffs, cost, status);
 }
 
 template <int N>
@@ -474,20 +305,12 @@ static hipError_t launch_time_cost_n(const PlanDev& pl, int64_t B, const double*
                                      double* cost, double* grad, int32_t* status,
                                      hipStream_t st) {
   const Layout lay = make_layout(N, pl.S, pl.D);
-  if (p.n_soft > 0) {
-    const size_t bytes = soft_cbuf_offset(lay) + sizeof(double) * pl.S * pl.D * N;
-    hipError_t e = prepare_lds(time_cost_kernel<N, true>, bytes);
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL((time_cost_kernel<N, true>), dim3(static_cast<unsigned>(B)),
-                       dim3(kWave), bytes, st, pl, df, times, p, cost, grad, status);
-  } else {
-    const size_t bytes = lay.bytes();
-    hipError_t e = prepare_lds(time_cost_kernel<N, false>, bytes);
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL((time_cost_kernel<N, false>), dim3(static_cast<unsigned>(B)),
-                       dim3(kWave), bytes, st, pl, df, times, p, cost, grad, status);
-  }
-  return hipGetLastError();
+  return with_soft(p.n_soft > 0, [&](auto soft) {
+    const size_t bytes =
+        soft ? soft_cbuf_offset(lay) + sizeof(double) * pl.S * pl.D * N : lay.bytes();
+    return launch(time_cost_kernel<N, decltype(soft)::value>, B, kWave, bytes, st, pl, df, times,
+                  p, cost, grad, status);
+  });
 }
 
 template <int N>
@@ -497,24 +320,12 @@ static hipError_t launch_time_opt_n(const PlanDev& pl, int64_t B, const double* 
                                     int32_t* solves, int32_t* result, int32_t* status,
                                     hipStream_t st) {
   const Layout lay = make_layout(N, pl.S, pl.D);
-  if (p.n_soft > 0) {
+  return with_soft(p.n_soft > 0, [&](auto soft) {
     const size_t bytes =
-        sbplx_state_offset(lay, pl.S, pl.D, N, true) + sbplx::state_bytes(pl.S);
-    hipError_t e = prepare_lds(time_optimize_kernel<N, true>, bytes);
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL((time_optimize_kernel<N, true>), dim3(static_cast<unsigned>(B)),
-                       dim3(kWave), bytes, st, pl, df, times, p, max_evals, cost, evals, solves,
-                       result, status);
-  } else {
-    const size_t bytes =
-        sbplx_state_offset(lay, pl.S, pl.D, N, false) + sbplx::state_bytes(pl.S);
-    hipError_t e = prepare_lds(time_optimize_kernel<N, false>, bytes);
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL((time_optimize_kernel<N, false>), dim3(static_cast<unsigned>(B)),
-                       dim3(kWave), bytes, st, pl, df, times, p, max_evals, cost, evals, solves,
-                       result, status);
-  }
-  return hipGetLastError();
+        sbplx_state_offset(lay, pl.S, pl.D, N, soft) + sbplx::state_bytes(pl.S);
+    return launch(time_optimize_kernel<N, decltype(soft)::value>, B, kWave, bytes, st, pl, df,
+                  times, p, max_evals, cost, evals, solves, result, status);
+  });
 }
 
 #define MTG_DISPATCH_N(N_, CALL)     \

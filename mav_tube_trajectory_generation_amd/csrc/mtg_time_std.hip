@@ -2,10 +2,12 @@
 // segment-time optimiser (objectiveFunctionTime / getCostAndGradientTime /
 // optimizeTime, nonlinear_impl:877-945, 2495-2584, 332-397) for the standard
 // vertex pattern, on the standard-pattern solver (stdp::Solver,
-// mtg_std_device.h).  Same objective, gradient modes and optimiser state
-// machine as the generic kernels (mtg_kernels.hip: time_cost_kernel,
-// time_optimize_kernel); instantiated for N = 10, r = 2..4, D = 1..3 (other
-// combinations run the generic kernels).
+// mtg_std_device.h) or its compile-time-S form (wave::Solver,
+// mtg_wave_device.h).  The gradient modes and the optimiser are the shared
+// drivers of mtg_time_device.h, which the generic kernels (mtg_kernels.hip:
+// time_cost_kernel, time_optimize_kernel) run too; this file holds the
+// objective and its evaluator.  Instantiated for N = 10, r = 2..4, D = 1..3
+// (other combinations run the generic kernels).
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -14,6 +16,7 @@
 #include "mtg_extrema_device.h"
 #include "mtg_sbplx_device.h"
 #include "mtg_std_device.h"
+#include "mtg_time_device.h"
 #include "mtg_wave_device.h"
 
 namespace mtg {
@@ -130,17 +133,41 @@ __device__ void std_load_fixed(wave::Solver<N, R, D, S>& sv, const double* __res
   wave::lds_order();
 }
 
-// Central-difference point gi (0 .. 2S-1) around base times Tb: segment
-// n = gi / 2 at T_n - inc (even gi) or T_n + inc (odd), both clamped to 0.1
-// when T_n <= 0.1 (nonlinear_impl:2529-2530).
-__device__ inline void std_set_fd_point(double* T, const double* Tb, int S, int gi, double inc,
-                                        int lane) {
-  const int n = gi >> 1;
-  for (int i = lane; i < S; i += kWave) {
-    const double Tn = Tb[i];
-    T[i] = i != n ? Tn : (Tn <= 0.1 ? 0.1 : ((gi & 1) ? Tn + inc : Tn - inc));
+// The evaluator of the shared drivers (mtg_time_device.h): either solver
+// with the drivers' hooks.  The evaluation point and the drivers' state share
+// the solver's aux() region.
+template <int N, int D, bool kSoft, class SV>
+struct StdEval : SV {
+  bool bad_ = false, not_spd_ = false;
+  __device__ __attribute__((always_inline)) double* T() const { return this->aux(); }
+  __device__ __attribute__((always_inline)) double* state(int S) const {
+    return this->aux() + S;
   }
-}
+  __device__ __attribute__((always_inline)) double eval(int S, const double* __restrict__ tab,
+                                                        double* cbuf, const mtg_time_params& p,
+                                                        double* viol) {
+    SV& sv = *this;
+    return std_objective<N, D, kSoft>(sv, tab, T(), S, p, cbuf, &bad_, &not_spd_, viol);
+  }
+  __device__ __attribute__((always_inline)) bool bad() const { return bad_; }
+  __device__ __attribute__((always_inline)) bool not_spd() const { return not_spd_; }
+  // getCostAndGradientTime (nonlinear_impl:2495-2584): d held at the base
+  // solution, only segment n's block of J_d = d^T R d changes.  One lane per
+  // segment energy, 2S of them into E.
+  __device__ __attribute__((always_inline)) void fixed_d_gradient(
+      int S, const double* Tb, const mtg_time_params& p, double* g, double* E) {
+    const int lane = this->lane;
+    const double inc = p.increment;
+    for (int i = lane; i < 2 * S; i += kWave) {
+      const int n = i >> 1;
+      E[i] = this->seg_energy(n, fd_time(Tb[n], i, inc));
+    }
+    __syncthreads();
+    for (int n = lane; n < S; n += kWave)
+      g[n] = p.w_d * (E[2 * n + 1] - E[2 * n]) / (2.0 * inc) + p.w_t * 1.0;
+    __syncthreads();
+  }
+};
 
 }  // namespace
 
@@ -159,73 +186,17 @@ static size_t time_std_opt_lds_bytes(int N, int S, int D, bool soft) {
 }
 
 // objectiveFunctionTime / getCostAndGradientTime on one trajectory per
-// workgroup (either solver; cbuf: the soft searches' LDS).
-template <int N, int D, bool kSoft, class SV>
-__device__ __attribute__((always_inline)) void time_cost_body(
-    SV& sv, int S, const double* __restrict__ tab, const double* __restrict__ fixed_vals,
-    const double* __restrict__ times, const mtg_time_params& p, double* __restrict__ cost,
-    double* __restrict__ grad, int32_t* __restrict__ status, double* cbuf) {
-  const int64_t b = blockIdx.x;
-  const int lane = sv.lane;
-  const int nf = N + S - 1;
-  double* T = sv.aux();  // evaluation point
-  double* Tb = T + S;    // base times
-  double* g = Tb + S;    // gradient
-  double* E = g + S;     // 2S segment energies (grad_mode 1)
-  std_load_fixed(sv, tab, fixed_vals + b * D * nf);
-  for (int i = lane; i < S; i += kWave) T[i] = Tb[i] = times[b * S + i];
-  const bool fd = grad && p.grad_mode == 2;
-  const int nevals = 1 + (fd ? 2 * S : 0);
-  double J0 = 0.0, Jlo = 0.0;
-  bool bad = false, not_spd = false;
-  for (int e = 0; e < nevals; ++e) {
-    if (e > 0) std_set_fd_point(T, Tb, S, e - 1, p.increment, lane);
-    double viol;
-    const double J = std_objective<N, D, kSoft>(sv, tab, T, S, p, cbuf, &bad, &not_spd, &viol);
-    if (e == 0) {
-      J0 = J;
-      if (bad) break;
-    } else if ((e - 1) & 1) {
-      if (lane == 0) g[(e - 1) >> 1] = (J - Jlo) / (2.0 * p.increment);
-    } else {
-      Jlo = J;
-    }
-  }
-  __syncthreads();
-  if (grad && p.grad_mode == 1 && !bad) {
-    // getCostAndGradientTime (nonlinear_impl:2495-2584): d held at the base
-    // solution, only segment n's block of J_d = d^T R d changes.
-    const double inc = p.increment;
-    for (int i = lane; i < 2 * S; i += kWave) {
-      const int n = i >> 1;
-      const double Tn = Tb[n];
-      const double tau = Tn <= 0.1 ? 0.1 : ((i & 1) ? Tn + inc : Tn - inc);
-      E[i] = sv.seg_energy(n, tau);
-    }
-    __syncthreads();
-    for (int n = lane; n < S; n += kWave)
-      g[n] = p.w_d * (E[2 * n + 1] - E[2 * n]) / (2.0 * inc) + p.w_t * 1.0;
-    __syncthreads();
-  }
-  if (lane == 0) {
-    if (cost) cost[b] = bad ? NAN : J0;
-    if (status)
-      status[b] = bad ? MTG_TRAJ_BAD_TIME : (not_spd ? MTG_TRAJ_NOT_SPD : MTG_TRAJ_OK);
-  }
-  if (grad && p.grad_mode != 0)
-    for (int i = lane; i < S; i += kWave) grad[b * S + i] = bad ? NAN : g[i];
-}
-
+// workgroup: time_cost_drive (mtg_time_device.h) around std_objective.
 template <int N, int R, int D, bool kSoft>
 __global__ __launch_bounds__(kWave) void time_cost_std_kernel(
     int S, const double* __restrict__ tab, const double* __restrict__ fixed_vals,
     const double* __restrict__ times, mtg_time_params p, double* __restrict__ cost,
     double* __restrict__ grad, int32_t* __restrict__ status) {
   extern __shared__ __attribute__((aligned(16))) double smem[];
-  StdSv<N, R, D> sv;
-  sv.init(S, smem, tab);
-  time_cost_body<N, D, kSoft>(sv, S, tab, fixed_vals, times, p, cost, grad, status,
-                              smem + (sv.L.n + 1) / 2 * 2);
+  StdEval<N, D, kSoft, StdSv<N, R, D>> ev;
+  ev.init(S, smem, tab);
+  std_load_fixed(ev, tab, fixed_vals + static_cast<int64_t>(blockIdx.x) * D * (N + S - 1));
+  time_cost_drive(ev, S, tab, smem + (ev.L.n + 1) / 2 * 2, times, p, cost, grad, status);
 }
 
 // The same on the compile-time-S solver (N = 10, r = 4, D = 3, S = 2..16).
@@ -237,144 +208,14 @@ __global__ __launch_bounds__(kWave) void time_cost_wave_kernel(
   using G = wave::Geo<N, R, D, S>;
   constexpr int CB = kSoft ? S * D * N + kMaxSoftConstraints * (N + 2) : 0;
   __shared__ __attribute__((aligned(16))) double sm[G::L_N + CB];
-  wave::Solver<N, R, D, S> sv;
-  sv.init(sm);
-  time_cost_body<N, D, kSoft>(sv, S, tab, fixed_vals, times, p, cost, grad, status,
-                              sm + G::L_N);
+  StdEval<N, D, kSoft, wave::Solver<N, R, D, S>> ev;
+  ev.init(sm);
+  std_load_fixed(ev, tab, fixed_vals + static_cast<int64_t>(blockIdx.x) * D * (N + S - 1));
+  time_cost_drive(ev, S, tab, sm + G::L_N, times, p, cost, grad, status);
 }
 
 // Batched segment-time optimisation (optimizeTime, nonlinear_impl:332-397):
-// bounds [0.1, 2 T0]; projected, scaled steepest descent on the grad_mode 2
-// gradient with an expand/backtrack step rule; `max_evals` objective
-// evaluations (NLopt maxeval semantics, nonlinear_impl:101; gradient
-// evaluations are not counted).  A state machine with one objective call
-// site, as time_optimize_kernel.
-template <int N, int D, bool kSoft, class SV>
-__device__ __attribute__((always_inline)) void time_optimize_body(
-    SV& sv, int S, const double* __restrict__ tab, const double* __restrict__ fixed_vals,
-    double* __restrict__ times_io, const mtg_time_params& p, int max_evals,
-    double* __restrict__ cost, int32_t* __restrict__ evals_out, int32_t* __restrict__ solves_out,
-    int32_t* __restrict__ result_out, int32_t* __restrict__ status, double* cbuf,
-    sbplx::State* sbs) {
-  const int64_t b = blockIdx.x;
-  const int lane = sv.lane;
-  const int nf = N + S - 1;
-  double* T = sv.aux();   // evaluation point
-  double* Tcur = T + S;   // accepted times
-  double* T0 = Tcur + S;  // initial times (bounds)
-  double* g = T0 + S;     // gradient at Tcur
-  double* gv = g + S;     // gradient of the violation at Tcur (hard constraints)
-  std_load_fixed(sv, tab, fixed_vals + b * D * nf);
-  for (int i = lane; i < S; i += kWave) T[i] = Tcur[i] = T0[i] = times_io[b * S + i];
-  constexpr double kLower = 0.1;  // kOptimizationTimeLowerBound (:370)
-  enum { kBase, kGrad, kTrial, kDone };
-  int phase = kBase, gi = 0, evals = 0, nsolve = 0, res = 0;
-  double f = 0.0, fv = 0.0, Jlo = 0.0, vlo = 0.0;
-  double alpha = 0.1;  // initial_stepsize_rel (polynomial_optimization_nonlinear.h:55)
-  bool bad = false, not_spd = false;
-  // LN_SBPLX (optimizer 1): the machine picks every point, lane 0 advances it
-  const bool sb = p.optimizer == 1;
-  sbplx::Machine mach{sbs};
-  if (sb) {
-    __syncthreads();
-    if (lane == 0)
-      mach.init(S, T, p.initial_stepsize_rel > 0.0 ? p.initial_stepsize_rel : 0.1, max_evals,
-                p.f_rel, p.f_abs);
-    __syncthreads();
-    if (sbs->done) phase = kDone;  // start outside the bounds (NLopt: FAILURE)
-  }
-  MTG_STAMP(460);
-  while (phase != kDone) {
-    double viol;
-    const double J = std_objective<N, D, kSoft>(sv, tab, T, S, p, cbuf, &bad, &not_spd, &viol);
-    ++nsolve;
-    if (sb) {
-      if (bad) break;
-      __syncthreads();
-      if (lane == 0) mach.resume(J, T);
-      __syncthreads();
-      if (sbs->done) break;
-      continue;
-    }
-    if (phase == kBase) {
-      f = J;
-      fv = viol;
-      evals = 1;
-      if (bad) break;
-      phase = kGrad;
-      gi = 0;
-    } else if (phase == kGrad) {
-      if (gi & 1) {
-        if (lane == 0) {
-          g[gi >> 1] = (J - Jlo) / (2.0 * p.increment);
-          gv[gi >> 1] = (viol - vlo) / (2.0 * p.increment);
-        }
-      } else {
-        Jlo = J;
-        vlo = viol;
-      }
-      if (++gi == 2 * S) phase = kTrial;
-    } else {  // trial point
-      ++evals;
-      // Feasibility first (hard constraints; viol is 0 otherwise).
-      if (viol == 0.0 ? (fv > 0.0 || J < f) : viol < fv) {
-        f = J;
-        fv = viol;
-        for (int i = lane; i < S; i += kWave) Tcur[i] = T[i];
-        alpha = fmin(alpha * 1.5, 1.0);
-        phase = kGrad;
-        gi = 0;
-      } else {
-        alpha *= 0.5;
-      }
-    }
-    __syncthreads();
-    // Next evaluation point.
-    if (phase == kGrad) {
-      std_set_fd_point(T, Tcur, S, gi, p.increment, lane);
-    } else if (phase == kTrial) {
-      if (!(evals < max_evals && alpha > 1e-9)) break;
-      // Scaled direction -g_n T0_n, normalised so the largest relative move
-      // is alpha; from an infeasible incumbent (hard constraints) the
-      // direction descends the violation instead.
-      const double* dir = fv > 0.0 ? gv : g;
-      double gmax = 0.0;
-      for (int i = 0; i < S; ++i) gmax = fmax(gmax, fabs(dir[i] * T0[i]));
-      if (!(gmax > 0.0)) break;
-      int moved = 0;
-      for (int i = 0; i < S; ++i) {
-        const double step = alpha * T0[i] * (dir[i] * T0[i]) / gmax;
-        double tn = Tcur[i] - step;
-        tn = fmin(fmax(tn, kLower), 2.0 * T0[i]);
-        if (tn != Tcur[i]) moved = 1;
-        if (lane == 0) T[i] = tn;
-      }
-      __syncthreads();
-      if (!moved) break;
-    }
-  }
-  __syncthreads();
-  MTG_STAMP(461);
-  if (sb) {  // NLopt's x and opt_f: the best point and its value
-    for (int i = lane; i < S; i += kWave) Tcur[i] = sbplx::best_x(sbs)[i];
-    f = sbs->minf;
-    evals = sbs->nevals;
-    res = sbs->result;
-    __syncthreads();
-  } else {
-    res = evals >= max_evals ? sbplx::kMaxEval : sbplx::kXtol;
-  }
-  for (int i = lane; i < S; i += kWave) times_io[b * S + i] = Tcur[i];
-  if (lane == 0) {
-    if (cost) cost[b] = bad ? NAN : f;
-    if (evals_out) evals_out[b] = evals;
-    if (solves_out) solves_out[b] = nsolve;
-    if (result_out) result_out[b] = res;
-    if (status)
-      status[b] = bad ? MTG_TRAJ_BAD_TIME : (not_spd ? MTG_TRAJ_NOT_SPD : MTG_TRAJ_OK);
-  }
-}
-
+// time_optimize_drive (mtg_time_device.h) around std_objective.
 template <int N, int R, int D, bool kSoft>
 __global__ __launch_bounds__(kWave) void time_optimize_std_kernel(
     int S, const double* __restrict__ tab, const double* __restrict__ fixed_vals,
@@ -382,13 +223,13 @@ __global__ __launch_bounds__(kWave) void time_optimize_std_kernel(
     double* __restrict__ cost, int32_t* __restrict__ evals_out, int32_t* __restrict__ solves_out,
     int32_t* __restrict__ result_out, int32_t* __restrict__ status) {
   extern __shared__ __attribute__((aligned(16))) double smem[];
-  StdSv<N, R, D> sv;
-  sv.init(S, smem, tab);
+  StdEval<N, D, kSoft, StdSv<N, R, D>> ev;
+  ev.init(S, smem, tab);
   auto* sbs = reinterpret_cast<sbplx::State*>(
       reinterpret_cast<char*>(smem) + (time_std_bytes(N, S, D, kSoft) + 15) / 16 * 16);
-  time_optimize_body<N, D, kSoft>(sv, S, tab, fixed_vals, times_io, p, max_evals, cost,
-                                  evals_out, solves_out, result_out, status,
-                                  smem + (sv.L.n + 1) / 2 * 2, sbs);
+  std_load_fixed(ev, tab, fixed_vals + static_cast<int64_t>(blockIdx.x) * D * (N + S - 1));
+  time_optimize_drive(ev, S, tab, smem + (ev.L.n + 1) / 2 * 2, times_io, p, max_evals, cost,
+                      evals_out, solves_out, result_out, status, sbs);
 }
 
 // The same on the compile-time-S solver (N = 10, r = 4, D = 3, S = 2..16).
@@ -402,91 +243,56 @@ __global__ __launch_bounds__(kWave) void time_optimize_wave_kernel(
   constexpr int CB = kSoft ? S * D * N + kMaxSoftConstraints * (N + 2) : 0;
   constexpr int SB = static_cast<int>(sbplx::state_bytes(S) / sizeof(double));
   __shared__ __attribute__((aligned(16))) double sm[(G::L_N + CB + 1) / 2 * 2 + SB];
-  wave::Solver<N, R, D, S> sv;
-  sv.init(sm);
-  time_optimize_body<N, D, kSoft>(sv, S, tab, fixed_vals, times_io, p, max_evals, cost,
-                                  evals_out, solves_out, result_out, status, sm + G::L_N,
-                                  reinterpret_cast<sbplx::State*>(sm + (G::L_N + CB + 1) / 2 * 2));
+  StdEval<N, D, kSoft, wave::Solver<N, R, D, S>> ev;
+  ev.init(sm);
+  std_load_fixed(ev, tab, fixed_vals + static_cast<int64_t>(blockIdx.x) * D * (N + S - 1));
+  time_optimize_drive(ev, S, tab, sm + G::L_N, times_io, p, max_evals, cost, evals_out,
+                      solves_out, result_out, status,
+                      reinterpret_cast<sbplx::State*>(sm + (G::L_N + CB + 1) / 2 * 2));
 }
 
 namespace {
-template <typename K>
-hipError_t prepare_lds_std(K kernel, size_t bytes) {
-  if (bytes > 65536)
-    return hipFuncSetAttribute(reinterpret_cast<const void*>(kernel),
-                               hipFuncAttributeMaxDynamicSharedMemorySize,
-                               static_cast<int>(bytes));
-  return hipSuccess;
-}
-
 template <int N, int R, int D>
 hipError_t time_cost_nrd(const PlanDev& pl, int64_t B, const double* df, const double* times,
                          const mtg_time_params& p, double* cost, double* grad, int32_t* status,
                          hipStream_t st) {
-  const bool soft = p.n_soft > 0;
-  const size_t bytes = time_std_lds_bytes(N, pl.S, D, soft);
-  if (soft) {
-    hipError_t e = prepare_lds_std(time_cost_std_kernel<N, R, D, true>, bytes);
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL((time_cost_std_kernel<N, R, D, true>), dim3(static_cast<unsigned>(B)),
-                       dim3(kWave), bytes, st, pl.S, pl.tab, df, times, p, cost, grad, status);
-  } else {
-    hipError_t e = prepare_lds_std(time_cost_std_kernel<N, R, D, false>, bytes);
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL((time_cost_std_kernel<N, R, D, false>), dim3(static_cast<unsigned>(B)),
-                       dim3(kWave), bytes, st, pl.S, pl.tab, df, times, p, cost, grad, status);
-  }
-  return hipGetLastError();
+  return with_soft(p.n_soft > 0, [&](auto soft) {
+    return launch(time_cost_std_kernel<N, R, D, decltype(soft)::value>, B, kWave,
+                  time_std_lds_bytes(N, pl.S, D, soft), st, pl.S, pl.tab, df, times, p, cost, grad,
+                  status);
+  });
 }
 
 template <int N, int R, int D>
 hipError_t time_opt_nrd(const PlanDev& pl, int64_t B, const double* df, double* times,
                         const mtg_time_params& p, int max_evals, double* cost, int32_t* evals,
                         int32_t* solves, int32_t* result, int32_t* status, hipStream_t st) {
-  const bool soft = p.n_soft > 0;
-  const size_t bytes = time_std_opt_lds_bytes(N, pl.S, D, soft);
-  if (soft) {
-    hipError_t e = prepare_lds_std(time_optimize_std_kernel<N, R, D, true>, bytes);
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL((time_optimize_std_kernel<N, R, D, true>),
-                       dim3(static_cast<unsigned>(B)), dim3(kWave), bytes, st, pl.S, pl.tab,
-                       df, times, p, max_evals, cost, evals, solves, result, status);
-  } else {
-    hipError_t e = prepare_lds_std(time_optimize_std_kernel<N, R, D, false>, bytes);
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL((time_optimize_std_kernel<N, R, D, false>),
-                       dim3(static_cast<unsigned>(B)), dim3(kWave), bytes, st, pl.S, pl.tab,
-                       df, times, p, max_evals, cost, evals, solves, result, status);
-  }
-  return hipGetLastError();
+  return with_soft(p.n_soft > 0, [&](auto soft) {
+    return launch(time_optimize_std_kernel<N, R, D, decltype(soft)::value>, B, kWave,
+                  time_std_opt_lds_bytes(N, pl.S, D, soft), st, pl.S, pl.tab, df, times, p,
+                  max_evals, cost, evals, solves, result, status);
+  });
 }
+
+// The compile-time-S kernels hold their LDS statically.
 template <int S>
 hipError_t time_cost_wave_s(const PlanDev& pl, int64_t B, const double* df, const double* times,
                             const mtg_time_params& p, double* cost, double* grad,
                             int32_t* status, hipStream_t st) {
-  if (p.n_soft > 0)
-    hipLaunchKernelGGL((time_cost_wave_kernel<10, 4, 3, S, true>), dim3(static_cast<unsigned>(B)),
-                       dim3(kWave), 0, st, pl.tab, df, times, p, cost, grad, status);
-  else
-    hipLaunchKernelGGL((time_cost_wave_kernel<10, 4, 3, S, false>),
-                       dim3(static_cast<unsigned>(B)), dim3(kWave), 0, st, pl.tab, df, times, p,
-                       cost, grad, status);
-  return hipGetLastError();
+  return with_soft(p.n_soft > 0, [&](auto soft) {
+    return launch(time_cost_wave_kernel<10, 4, 3, S, decltype(soft)::value>, B, kWave, 0, st,
+                  pl.tab, df, times, p, cost, grad, status);
+  });
 }
 
 template <int S>
 hipError_t time_opt_wave_s(const PlanDev& pl, int64_t B, const double* df, double* times,
                            const mtg_time_params& p, int max_evals, double* cost, int32_t* evals,
                            int32_t* solves, int32_t* result, int32_t* status, hipStream_t st) {
-  if (p.n_soft > 0)
-    hipLaunchKernelGGL((time_optimize_wave_kernel<10, 4, 3, S, true>),
-                       dim3(static_cast<unsigned>(B)), dim3(kWave), 0, st, pl.tab, df, times, p,
-                       max_evals, cost, evals, solves, result, status);
-  else
-    hipLaunchKernelGGL((time_optimize_wave_kernel<10, 4, 3, S, false>),
-                       dim3(static_cast<unsigned>(B)), dim3(kWave), 0, st, pl.tab, df, times, p,
-                       max_evals, cost, evals, solves, result, status);
-  return hipGetLastError();
+  return with_soft(p.n_soft > 0, [&](auto soft) {
+    return launch(time_optimize_wave_kernel<10, 4, 3, S, decltype(soft)::value>, B, kWave, 0, st,
+                  pl.tab, df, times, p, max_evals, cost, evals, solves, result, status);
+  });
 }
 
 // The compile-time-S kernels where the C2 kernel exists (MTG_STD_RUNTIME_S=1

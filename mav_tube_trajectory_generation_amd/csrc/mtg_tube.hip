@@ -186,38 +186,19 @@ size_t tube_lds_bytes(int N, int S) {
 }
 
 namespace {
-template <typename K>
-hipError_t prepare_lds(K kernel, size_t bytes) {
-  if (bytes > 65536)
-    return hipFuncSetAttribute(reinterpret_cast<const void*>(kernel),
-                               hipFuncAttributeMaxDynamicSharedMemorySize,
-                               static_cast<int>(bytes));
-  return hipSuccess;
-}
-
 template <int N>
 hipError_t residuals_n(const TubeArgs& a, const double* x, double* resid, hipStream_t st) {
-  const size_t bytes = tube_lds_bytes(N, a.S);
-  hipError_t e = prepare_lds(tube_residuals_kernel<N>, bytes);
-  if (e != hipSuccess) return e;
-  hipLaunchKernelGGL(tube_residuals_kernel<N>, dim3(static_cast<unsigned>(a.B)), dim3(kWave),
-                     bytes, st, a.S, a.r, a.rep, a.tab, a.positions, a.fixed_vals, a.times_cp,
-                     a.times, a.radii, x, resid);
-  return hipGetLastError();
+  return launch(tube_residuals_kernel<N>, a.B, kWave, tube_lds_bytes(N, a.S), st, a.S, a.r, a.rep,
+                a.tab, a.positions, a.fixed_vals, a.times_cp, a.times, a.radii, x, resid);
 }
 
 template <typename K>
 hipError_t solve_launch(K kernel, int threads, const TubeArgs& a, double tol, int max_iter,
                         double* x, double* coeffs, double* cost, int32_t* iters, int32_t* status,
                         hipStream_t st) {
-  const size_t bytes = tube_lds_bytes(a.N, a.S);
-  hipError_t e = prepare_lds(kernel, bytes);
-  if (e != hipSuccess) return e;
-  hipLaunchKernelGGL(kernel, dim3(static_cast<unsigned>(a.B)), dim3(threads), bytes, st, a.S,
-                     a.r, a.rep, a.tab, a.positions, a.fixed_vals, a.times_cp, a.times, a.radii,
-                     tol, max_iter, a.skip, x, coeffs, cost, iters, status, a.warm, a.warm_ok,
-                     a.order);
-  return hipGetLastError();
+  return launch(kernel, a.B, threads, tube_lds_bytes(a.N, a.S), st, a.S, a.r, a.rep, a.tab,
+                a.positions, a.fixed_vals, a.times_cp, a.times, a.radii, tol, max_iter, a.skip, x,
+                coeffs, cost, iters, status, a.warm, a.warm_ok, a.order);
 }
 
 // The compile-time-S kernels unless MTG_TUBE_RUNTIME_S=1 (A/B runs).

@@ -292,3 +292,70 @@ def test_time_cost_wave_kernels_every_s(ctx, dev, oracle, S):
         tol = 1e-9 if times[b].min() > 0.5 else 1e-6
         assert rel_err(cost[b], J) <= tol, (S, b)
         assert np.max(np.abs(grad[b] - g)) <= 1e-5 * np.max(np.abs(g)) + 1e-9, (S, b)
+
+
+def test_time_cost_bad_central_difference_point(ctx, dev, oracle, kernel):
+    """A central-difference point with a non-positive time (increment >= T_n
+    > 0.1): the row is MTG_TRAJ_BAD_TIME with NaN cost and gradient on every
+    kernel; the other row is unaffected."""
+    import mav_tube_trajectory_generation_amd as mtg
+    S, B, inc = 3, 2, 0.2
+    mask, fixed, times, _ = _batch(S, B, 700)
+    times[0, 1] = 0.15  # its lower point is 0.15 - 0.2 < 0
+    # Every evaluated time of row 1 stays above 0.5 (well-conditioned bounds).
+    times[1] = np.maximum(times[1], 1.0)
+    plan = mtg.LinearPlan(ctx, N, D, R, S, mask).set_kernel(kernel)
+    out = plan.time_cost(torch.from_numpy(fixed).to(dev), torch.from_numpy(times).to(dev),
+                         grad_mode=2, increment=inc)
+    status = out["status"].cpu().numpy()
+    cost = out["cost"].cpu().numpy()
+    grad = out["grad"].cpu().numpy()
+    assert status[0] == 1 and status[1] == 0, status  # MTG_TRAJ_BAD_TIME, MTG_TRAJ_OK
+    assert np.isnan(cost[0]) and np.isnan(grad[0]).all() and grad[0].shape == (S,), (cost, grad)
+    J, g = oracle.time_cost(N, R, standard_vertices(N, S, D, 701), times[1], grad_mode=2,
+                            increment=inc)
+    assert rel_err(cost[1], J) <= 1e-9
+    assert np.max(np.abs(grad[1] - g)) <= 1e-6 * np.max(np.abs(g)) + 1e-9, (grad[1], g)
+
+
+def test_time_generic_driver_off_n10(ctx, dev, oracle):
+    """N = 6 (no standard-pattern time kernels: the generic kernels under
+    AUTO): the cost with every gradient mode, the descent and LN_SBPLX, with
+    the bounds of test_time_cost_vs_oracle (well-conditioned rows),
+    test_time_optimize_vs_reference_driver and test_sbplx_generic_kernel."""
+    import mav_tube_trajectory_generation_amd as mtg
+    n, d, r, S, B, E = 6, 2, 2, 3, 4, 10
+    mask, fixed, times, _ = mtg.generate_random_problems(n, d, S, B, seed0=300)
+    times = np.maximum(times, 0.7)  # every central-difference point above 0.5
+    plan = mtg.LinearPlan(ctx, n, d, r, S, mask)
+    fd, td = torch.from_numpy(fixed).to(dev), torch.from_numpy(times).to(dev)
+    vs = [standard_vertices(n, S, d, 300 + b) for b in range(B)]
+    for grad_mode in (0, 1, 2):
+        out = plan.time_cost(fd, td, grad_mode=grad_mode, increment=0.1, w_d=0.1, w_t=1.0)
+        assert (out["status"].cpu().numpy() == 0).all()
+        cost = out["cost"].cpu().numpy()
+        for b in range(B):
+            J, g = oracle.time_cost(n, r, vs[b], times[b], grad_mode=grad_mode, increment=0.1,
+                                    w_d=0.1, w_t=1.0)
+            assert rel_err(cost[b], J) <= 1e-9, (grad_mode, b)
+            if grad_mode:
+                gg = out["grad"].cpu().numpy()[b]
+                assert np.max(np.abs(gg - g)) <= 1e-6 * np.max(np.abs(g)) + 1e-9, (grad_mode, b)
+    out = {k: v.cpu().numpy() for k, v in plan.time_optimize(fd, td, max_evals=E).items()}
+    for b in range(B):
+        Tr, fr, er = optimize_reference(oracle, n, r, vs[b], times[b], E)
+        assert out["evals"][b] == er, b
+        assert np.max(np.abs(out["times"][b] - Tr) / Tr) <= 1e-6, (b, out["times"][b], Tr)
+        assert rel_err(out["cost"][b], fr) <= 1e-6, b
+        Tc, fc, ec = oracle.time_optimize(n, r, vs[b], times[b], E)
+        assert ec == out["evals"][b] and np.max(np.abs(out["times"][b] - Tc) / Tc) <= 1e-6, b
+    out = {k: v.cpu().numpy()
+           for k, v in plan.time_optimize(fd, td, max_evals=E, optimizer="sbplx").items()}
+    agree = 0
+    for b in range(B):
+        Tc, fc, ec, rc, _ = oracle.time_optimize_sbplx(n, r, vs[b], times[b], E)
+        if (ec == out["evals"][b] and rc == out["result"][b]
+                and np.max(np.abs(out["times"][b] - Tc) / Tc) <= 1e-6):
+            assert rel_err(out["cost"][b], fc) <= 1e-6, b
+            agree += 1
+    assert agree >= B - 1, agree
