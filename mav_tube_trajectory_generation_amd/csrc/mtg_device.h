@@ -555,10 +555,21 @@ struct Traj {
   // registers; half h covers coefficients / rows k in [hM, hM + M):
   //   c_s[d][k] = sum_j A(1)^-1[k][j] T_s^(j mod M - k) e_j   (coefficients,
   //               linear_impl:254-275; written to `out` when kCoeffs)
-  //   cost     += e_k (H_s e)_k                               (computeCost,
-  //               linear_impl:113-130: 0.5 c^T Q c == 0.5 e^T H e)
+  //   cost     += T_s^(1-2r) sum_ij g_i g_j / (i + j - 2r + 1), i, j >= r,
+  //               g_i = base(r, i) c_i T_s^i                  (computeCost,
+  //               linear_impl:113-130: 0.5 c^T Q c as the reference forms it,
+  //               with computeQuadraticCostJacobian's 2 and the 0.5 cancelled
+  //               and T scaled out; the half-0 lane of a pair sums it)
+  // 0.5 e^T H_s e is the same number but not in FP64: next to a segment at
+  // the lower time bound the vertex derivatives reach 1e8, the terms of
+  // e^T H e on the long neighbour cancel by ten digits and the cost comes out
+  // wrong from the fourth digit on (test_linear_exact_gpu.py, edge_odd and
+  // fd_low).  In the coefficients that cancellation has already happened in
+  // the well-conditioned map A^-1, and Q is only the (N-r)-order Hilbert form.
+  // kEnergyForm keeps 0.5 e^T H e, cost += e_k (H_s e)_k: the kernels of the
+  // soft-constraint objective still use it.
   // Returns computeCost() on every lane.
-  template <bool kCoeffs>
+  template <bool kCoeffs, bool kEnergyForm = false>
   __device__ double coeffs_and_cost(const double* __restrict__ tab,
                                     double* __restrict__ out) const {
     (void)tab;
@@ -570,18 +581,50 @@ struct Traj {
       double e[N];
 #pragma unroll
       for (int j = 0; j < N; ++j) e[j] = dval(s + j / M, j % M, d);
-      const double* tH = tabH() + h * M * N;
-      const double* ph = pw() + s * PWN + (N - 1) + 1 - 2 * r;  // T^(1-2r+q)
-      double cs = 0.0;
-      // Rolled over rows (N table values live per row, not N*M).
+      if constexpr (kEnergyForm) {
+        const double* tH = tabH() + h * M * N;
+        const double* ph = pw() + s * PWN + (N - 1) + 1 - 2 * r;  // T^(1-2r+q)
+        double cs = 0.0;
+        // Rolled over rows (N table values live per row, not N*M).
 #pragma unroll 1
-      for (int kk = 0; kk < M; ++kk) {
-        double hk = 0.0;
+        for (int kk = 0; kk < M; ++kk) {
+          double hk = 0.0;
 #pragma unroll
-        for (int j = 0; j < N; ++j) hk += tH[kk * N + j] * ph[kk + (j % M)] * e[j];
-        cs += hk * dval(s + h, kk, d);
+          for (int j = 0; j < N; ++j) hk += tH[kk * N + j] * ph[kk + (j % M)] * e[j];
+          cs += hk * dval(s + h, kk, d);
+        }
+        acc += cs;
+      } else if (h == 0) {
+        const double* pu = pw() + s * PWN + (N - 1);  // T^q
+        double f[N], g[N];
+#pragma unroll
+        for (int j = 0; j < N; ++j) f[j] = e[j] * pu[j % M];
+        // g[ii] belongs to coefficient i = r + ii (zero past N - 1): the
+        // register indices stay compile-time with r a run-time number.
+#pragma unroll
+        for (int ii = 0; ii < N; ++ii) {
+          const int i = r + ii;
+          double hi = 0.0, base = 1.0;
+          if (i < N) {
+            const double* tA = tabA() + i * N;
+#pragma unroll
+            for (int j = 0; j < N; ++j) hi = fma(tA[j], f[j], hi);
+#pragma unroll
+            for (int m = 0; m < M; ++m)
+              if (m < r) base *= static_cast<double>(i - m);
+          }
+          g[ii] = base * hi;
+        }
+        double q = 0.0;
+#pragma unroll
+        for (int ii = 0; ii < N; ++ii) {
+          double t = g[ii] * (1.0 / (2 * ii + 1));
+#pragma unroll
+          for (int jj = ii + 1; jj < N; ++jj) t = fma(2.0 / (ii + jj + 1), g[jj], t);
+          q = fma(t, g[ii], q);
+        }
+        acc += q * pu[1 - 2 * r];
       }
-      acc += cs;
       if (kCoeffs) {
         // T^(l - k) for l in [0, M), k = hM + kk.
         const double* tA = tabA() + h * M * N;
@@ -595,7 +638,8 @@ struct Traj {
         }
       }
     }
-    return 0.5 * wave_sum(acc);
+    if constexpr (kEnergyForm) return 0.5 * wave_sum(acc);
+    return wave_sum(acc);
   }
 
   __device__ double cost(const double* __restrict__ tab) const {

@@ -39,7 +39,7 @@ __device__ double free_objective(Traj<N>& t, const double* __restrict__ tab,
                                  const mtg_time_params& p, int mode, double* cbuf) {
   double c;
   if constexpr (kSoft) {
-    c = t.template coeffs_and_cost<true>(tab, cbuf);  // coefficients into LDS
+    c = t.template coeffs_and_cost<true, true>(tab, cbuf);  // coefficients into LDS
   } else {
     c = t.cost(tab);
   }

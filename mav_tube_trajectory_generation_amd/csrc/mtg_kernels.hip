@@ -162,7 +162,8 @@ __device__ double objective_at(Traj<N>& t, const double* __restrict__ tab,
   t.solve();
   double J;
   if constexpr (kSoft) {
-    J = t.template coeffs_and_cost<true>(tab, cbuf);  // coefficients into LDS
+    // 0.5 e^T H e as before (Traj::coeffs_and_cost); coefficients into LDS
+    J = t.template coeffs_and_cost<true, true>(tab, cbuf);
   } else {
     J = t.cost(tab);
   }

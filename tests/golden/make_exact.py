@@ -43,10 +43,12 @@ def gauss_jordan(A, m, ncols):
     return A
 
 
-def exact_solve(N, r, mask, vals, times):
+def exact_R(N, r, times):
+    """Exact R = sum over segments of H_s = A_s^-T Q_s A_s^-1 scattered into
+    (vertex, derivative) order, [(S+1) N/2]^2, and the exact A_s^-1 per
+    segment; times are taken as the FP64 numbers they are."""
     M = N // 2
     S = len(times)
-    D = vals.shape[2]
     T = [F(float(t)) for t in times]
     n = (S + 1) * M
     R = [[F(0)] * n for _ in range(n)]
@@ -71,23 +73,52 @@ def exact_solve(N, r, mask, vals, times):
         for a in range(N):
             for b in range(N):
                 R[s * M + a][s * M + b] += H[a][b]
+    return R, Ais
+
+
+def exact_solution(N, r, mask, vals, times):
+    """The exact minimiser, in Fractions: dict(R, Ais, fr (the free indices
+    in (vertex, derivative) order), x [D][(S+1) N/2] all vertex derivatives,
+    cost = 1/2 sum_d x^T R x)."""
+    M = N // 2
+    S = len(times)
+    D = vals.shape[2]
+    R, Ais = exact_R(N, r, times)
+    n = (S + 1) * M
     fixed = mask.reshape(-1).astype(bool)
     fr = [i for i in range(n) if not fixed[i]]
     fx = [i for i in range(n) if fixed[i]]
-    out = np.zeros((S, D, N))
-    for d in range(D):
-        x = [F(0)] * n
+    xs = [[F(0)] * n for _ in range(D)]
+    for x, d in zip(xs, range(D)):
         for i in fx:
             x[i] = F(float(vals[i // M, i % M, d]))
-        A = [[R[i][j] for j in fr] + [-sum(R[i][j] * x[j] for j in fx)] for i in fr]
-        A = gauss_jordan(A, len(fr), len(fr) + 1)
+    # one elimination, D right-hand sides
+    A = [[R[i][j] for j in fr] + [-sum(R[i][j] * x[j] for j in fx if R[i][j] != 0) for x in xs]
+         for i in fr]
+    A = gauss_jordan(A, len(fr), len(fr) + D)
+    for d, x in enumerate(xs):
         for t, i in enumerate(fr):
-            x[i] = A[t][len(fr)]
+            x[i] = A[t][len(fr) + d]
+    cost = sum(x[i] * R[i][j] * x[j] for x in xs for i in range(n) for j in range(n)
+               if R[i][j] != 0) / 2
+    return dict(R=R, Ais=Ais, fr=fr, x=xs, cost=cost)
+
+
+def exact_coeffs(N, sol):
+    """Segment coefficients [S, D, N] of an exact_solution, rounded once."""
+    M = N // 2
+    S, D = len(sol["Ais"]), len(sol["x"])
+    out = np.zeros((S, D, N))
+    for d, x in enumerate(sol["x"]):
         for s in range(S):
             e = x[s * M:(s + 2) * M]
             for k in range(N):
-                out[s, d, k] = float(sum(Ais[s][k][j] * e[j] for j in range(N)))
+                out[s, d, k] = float(sum(sol["Ais"][s][k][j] * e[j] for j in range(N)))
     return out
+
+
+def exact_solve(N, r, mask, vals, times):
+    return exact_coeffs(N, exact_solution(N, r, mask, vals, times))
 
 
 def main():
