@@ -69,6 +69,78 @@ struct ExtEmit {
   bool single;
 };
 
+// f and f' at t in product form: f = sum_d p_d^(K) p_d^(K+1) from the Horner
+// sums of p_d^(K) and its two derivatives (single: f = p^(K+1)).
+template <int N, int K>
+__device__ inline void ext_f_product(const double* c, int D, bool single, double t, double& f,
+                                     double& df) {
+  f = 0.0;
+  df = 0.0;
+#pragma unroll
+  for (int d = 0; d < kMaxD; ++d) {
+    if (d >= D) break;
+    const double* cd = c + d * N;
+    double v = ext_falling(K, N - 1) * cd[N - 1], d1 = 0.0, d2 = 0.0;  // p, p', p'' / 2
+#pragma unroll
+    for (int i = N - 2; i >= K; --i) {
+      d2 = fma(d2, t, d1);
+      d1 = fma(d1, t, v);
+      v = fma(v, t, ext_falling(K, i) * cd[i]);
+    }
+    if (single) {
+      f = d1;
+      df = 2.0 * d2;
+    } else {
+      f = fma(v, d1, f);
+      df = fma(d1, d1, fma(2.0 * v, d2, df));
+    }
+  }
+}
+
+// A root t of f, isolated by the search in [ta, te], polished on f in
+// product form.  The search works on the convolved coefficients of f, whose
+// Horner sum carries eps (sum |a_i| t^i)(sum |a'_i| t^i): with strongly
+// cancelling p (Chebyshev-like) that floor is wider than a node, Laguerre
+// stops where it starts (the node's middle, up to 1.5e-2 T off at N = 12) or
+// lands 1e-6 T off, as the reference's root finder does.  In product form the
+// error is eps (|p'| sum |a_i| t^i + |p| sum |a'_i| t^i), orders of magnitude
+// smaller.  If the product form changes sign over the node, Newton's method
+// safeguarded by that bracket (bisection when a step leaves it) finds the
+// root in it.  If not (a root on a dyadic point that the search found just
+// right of it), plain Newton steps may move the root by T / 64 within [0, T];
+// a step that goes further ends the polish.
+template <int N, int K>
+__device__ inline double ext_polish_root(const double* c, int D, bool single, double t, double ta,
+                                         double te, double T) {
+  double f, df, fa, fe;
+  ext_f_product<N, K>(c, D, single, ta, fa, df);
+  ext_f_product<N, K>(c, D, single, te, fe, df);
+  if ((fa < 0.0 && fe > 0.0) || (fa > 0.0 && fe < 0.0)) {
+    double lo = ta, hi = te;
+    if (!(t > lo && t < hi)) t = 0.5 * (lo + hi);
+    for (int it = 0; it < 64; ++it) {
+      ext_f_product<N, K>(c, D, single, t, f, df);
+      if (f == 0.0) break;
+      if ((f > 0.0) == (fa > 0.0)) lo = t; else hi = t;
+      double tn = df != 0.0 ? t - f / df : 0.5 * (lo + hi);
+      if (!(tn > lo && tn < hi)) tn = 0.5 * (lo + hi);
+      const bool done = fabs(tn - t) <= 0x1p-50 * T;
+      t = tn;
+      if (done) break;
+    }
+    return t;
+  }
+  const double lo = fmax(0.0, t - T * 0x1p-6), hi = fmin(T, t + T * 0x1p-6);
+  for (int it = 0; it < 4; ++it) {
+    ext_f_product<N, K>(c, D, single, t, f, df);
+    if (!(df != 0.0)) break;
+    const double tn = t - f / df;
+    if (!(tn >= lo && tn <= hi)) break;
+    t = tn;
+  }
+  return t;
+}
+
 // One lane's share of segment s: the endpoint candidates (part 0: t = 0,
 // last part: t = T) and the real roots of f = sum_d p_d^(K) p_d^(K+1) in its
 // dyadic part [part / 2^log2parts, (part + 1) / 2^log2parts) of the segment.
@@ -79,7 +151,7 @@ struct ExtEmit {
 // +inf).  lb: a value |p^(K)|^2 attains somewhere on the trajectory (0 if
 // none is known); without kMin, nodes whose upper bound lies below it are
 // pruned, which never drops the trajectory's maximum.
-template <int N, int K, bool kMin = false, bool kEmit = false>
+template <int N, int K, bool kMin = false, bool kEmit = false, bool kRightEnd = true>
 __device__ __attribute__((always_inline)) inline void ext_segment_search(const double* c, int D, double T, int part, int parts,
                                           int log2parts, double& best_v, double& best_t,
                                           double& min_v, double& min_t, double lb = 0.0,
@@ -306,8 +378,16 @@ __device__ __attribute__((always_inline)) inline void ext_segment_search(const d
         else descend = true;
       }
       if (root >= 0.0) {
-        const double ur = fma(w0, root, u0);
-        take(ext_mag2<N, K>(c, D, ur * T), ur * T);
+        double tr = fma(w0, root, u0) * T;
+        // (kRightEnd = false also leaves the polish out.)
+        if constexpr (kRightEnd) {
+          bool single = false;
+          if constexpr (kEmit) single = em->single;
+          if (var == 1)
+            tr = ext_polish_root<N, K>(c, D, single, tr, fma(w0, a, u0) * T,
+                                       fma(w0, e, u0) * T, T);
+        }
+        take(ext_mag2<N, K>(c, D, tr), tr);
       }
       if (descend) {
         ++level;
@@ -320,6 +400,21 @@ __device__ __attribute__((always_inline)) inline void ext_segment_search(const d
       }
       if (level == 0) break;
       ++idx;
+    }
+  }
+  // The part's right end (the next part's left end), after the part's roots
+  // in ascending time.  A root of f on a part boundary is otherwise taken
+  // only if the next part's first coefficient is exactly 0.0: with rounding
+  // the part left of it can end on +1e-17 and the part right of it start on
+  // -1e-17, neither sees a sign change, and the maximum there is lost.  g at
+  // the boundary differs from g at such a root by the square of that
+  // rounding.  (The segment's own end is taken above; the candidate list
+  // runs one part.)  kRightEnd = false leaves it and the polish of the
+  // roots out: see ext_trajectory_max_wave.
+  if constexpr (!kEmit && kRightEnd) {
+    if (part < parts - 1) {
+      const double te = ldexp(T * (part + 1), -log2parts);
+      take(ext_mag2<N, K>(c, D, te), te);
     }
   }
 #ifdef MTG_STAMPS
@@ -363,8 +458,15 @@ __device__ __attribute__((always_inline)) inline double ext_trajectory_max_wave(
   for (int item = lane; item < S * parts; item += 64) {
     const int s = item >> log2parts, part = item & (parts - 1);
     double v = -1.0, t = 0.0, mv = 0.0, mt = 0.0;
-    ext_segment_search<N, K>(coeffs + s * D * N, D, times[s], part, parts, log2parts, v, t, mv,
-                             mt, lb, nullptr, pst);
+    // Without the parts' right-end candidates and the product-form polish of
+    // the roots (kRightEnd = false), so a
+    // maximum on a part boundary can still be lost here as described in
+    // ext_segment_search: with them, time_optimize_kernel<10, true> stopped
+    // making progress on the GPU (the stall of DESIGN.md §3, "Known accuracy
+    // gap"), so the generic time and free kernels keep the search they had
+    // until that stall is explained.
+    ext_segment_search<N, K, false, false, false>(coeffs + s * D * N, D, times[s], part, parts,
+                                                  log2parts, v, t, mv, mt, lb, nullptr, pst);
     best = fmax(best, v);
   }
 #ifdef MTG_STAMPS
