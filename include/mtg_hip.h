@@ -69,9 +69,11 @@ enum {
                                 (tube QCQP: its KKT system broke down twice,
                                 plain and regularised, away from the optimum) */
   MTG_TRAJ_NOT_CONVERGED = 3, /* interior-point solve hit its iteration cap */
-  MTG_TRAJ_NEAR_OPTIMAL = 4   /* interior-point solve stopped where its KKT
+  MTG_TRAJ_NEAR_OPTIMAL = 4,  /* interior-point solve stopped where its KKT
                                  system broke down, every residual within
                                  1e3 x tol: usable, not converged to tol */
+  MTG_TRAJ_BAD_SEGMENTS = 5   /* ragged batch: the row's segment count is
+                                 outside the entry point's range */
 };
 
 typedef struct mtg_ctx mtg_ctx;
@@ -289,6 +291,76 @@ int mtg_time_optimize_ex(const mtg_plan* plan, int64_t B, const double* fixed_va
                          double* times_io, const mtg_time_params* params, int max_evals,
                          double* cost, int32_t* evals, int32_t* solves, int32_t* result,
                          int32_t* status, void* stream);
+
+/* ------------------------------------------------------------------------
+ * Ragged batches: one launch over trajectories of different segment counts.
+ * Standard vertex pattern only (start and end vertex fixed to order M-1,
+ * intermediate vertices position only: createRandomVertices /
+ * makeStartOrEnd, vertex.cpp:27-82, 147-153); every other pattern needs a
+ * uniform mtg_plan.  The reference has no batch; per trajectory the entry
+ * points replace what mtg_linear_solve / mtg_time_cost /
+ * mtg_time_optimize_ex replace.
+ *
+ * The plan fixes S_max; trajectory b has S_b = seg_counts[b] segments
+ * (device int32, read by the kernels only: the host never sees the counts,
+ * so a captured launch may be replayed over other counts).  With
+ * nf_max = 2M + S_max - 1 and np_max = (S_max - 1)(M - 1), all arrays are
+ * padded rectangles (device):
+ *   seg_counts  B                  1 <= S_b <= S_max
+ *   fixed_vals  B x D x nf_max     each row d holds nf_b = 2M + S_b - 1
+ *                                  values at the front, in mtg_linear_solve's
+ *                                  order (vertex 0 derivatives 0..M-1,
+ *                                  intermediate positions, vertex S_b
+ *                                  derivatives 0..M-1); the rest is never read
+ *   times       B x S_max          the first S_b are read; the rest is never
+ *                                  read (and may be NaN)
+ *   coeffs      B x S_max x D x N  segments < S_b as mtg_linear_solve writes
+ *                                  them, segments >= S_b written 0.0
+ *   free_vals   B x D x np_max     nullable; each row's first
+ *                                  (S_b - 1)(M - 1) entries, the rest 0.0
+ *   cost, status  B                nullable, as mtg_linear_solve
+ * A row whose count is outside [1, S_max] gets MTG_TRAJ_BAD_SEGMENTS; a row
+ * with a time that is not positive MTG_TRAJ_BAD_TIME.  Either way the row's
+ * outputs are NaN over its whole padded row (padding included) and nothing
+ * outside the row is touched.
+ *
+ * Coverage: N in {4, 6, 8, 10, 12}, D <= 4, r < N/2, 1 <= S_max <= 64
+ * (MTG_ERR_INVALID_ARG below 1, MTG_ERR_UNSUPPORTED above 64).  The plan
+ * copies the context's device id and table pointer for (N, r) at creation
+ * and never dereferences ctx afterwards, so it may be destroyed after its
+ * context (launching after the context is gone is an error of the caller:
+ * the table belongs to the context).  One 64-lane workgroup per trajectory;
+ * LDS per workgroup is sized by S_max, not S_b, and a launch lasts as long as
+ * its longest trajectory's chain.
+ */
+typedef struct mtg_ragged_plan mtg_ragged_plan;
+int mtg_ragged_plan_create(mtg_ctx* ctx, int N, int D, int r, int S_max,
+                           mtg_ragged_plan** out);
+int mtg_ragged_plan_destroy(mtg_ragged_plan* plan);
+int mtg_ragged_plan_counts(const mtg_ragged_plan* plan, int* nf_max, int* np_max);
+int mtg_ragged_linear_solve(const mtg_ragged_plan* plan, int64_t B, const int32_t* seg_counts,
+                            const double* fixed_vals, const double* times, double* coeffs,
+                            double* cost, double* free_vals, int32_t* status, void* stream);
+/* mtg_time_cost and mtg_time_optimize_ex over a ragged batch: N = 10,
+ * r = 2..4, D <= 3 (MTG_ERR_UNSUPPORTED otherwise, and where the LDS for
+ * S_max, with the LN_SBPLX state for the optimiser, exceeds the kernels'
+ * budget); n_soft > 0 or hard_constraints != 0 is MTG_ERR_UNSUPPORTED.
+ * Rows need 2 <= S_b <= S_max, else MTG_TRAJ_BAD_SEGMENTS: cost NaN, the
+ * whole gradient row NaN; the optimiser leaves the row's times_io untouched
+ * and reports evals 0, solves 0, result -1.
+ *   grad      B x S_max  (grad_mode != 0) entries >= S_b written 0.0
+ *   times_io  B x S_max  entries >= S_b keep their input bits
+ * The other arguments are as in mtg_time_cost / mtg_time_optimize_ex (both
+ * optimisers through params->optimizer). */
+int mtg_ragged_time_cost(const mtg_ragged_plan* plan, int64_t B, const int32_t* seg_counts,
+                         const double* fixed_vals, const double* times,
+                         const mtg_time_params* params, double* cost, double* grad,
+                         int32_t* status, void* stream);
+int mtg_ragged_time_optimize(const mtg_ragged_plan* plan, int64_t B, const int32_t* seg_counts,
+                             const double* fixed_vals, double* times_io,
+                             const mtg_time_params* params, int max_evals, double* cost,
+                             int32_t* evals, int32_t* solves, int32_t* result, int32_t* status,
+                             void* stream);
 
 /* ------------------------------------------------------------------------
  * Free-derivative objectives of PolynomialOptimizationNonLinear (the NLopt

@@ -204,6 +204,17 @@ SIGNATURES = {
     "mtg_time_optimize_ex": (ctypes.c_int, [_vp, ctypes.c_int64, _vp, _vp,
                                             ctypes.POINTER(TimeParams), ctypes.c_int, _vp, _vp,
                                             _vp, _vp, _vp, _vp]),
+    "mtg_ragged_plan_create": (ctypes.c_int, [_vp, ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                                              ctypes.c_int, ctypes.POINTER(_vp)]),
+    "mtg_ragged_plan_destroy": (ctypes.c_int, [_vp]),
+    "mtg_ragged_plan_counts": (ctypes.c_int, [_vp, _ip, _ip]),
+    "mtg_ragged_linear_solve": (ctypes.c_int, [_vp, ctypes.c_int64, _vp, _vp, _vp, _vp, _vp, _vp,
+                                               _vp, _vp]),
+    "mtg_ragged_time_cost": (ctypes.c_int, [_vp, ctypes.c_int64, _vp, _vp, _vp,
+                                            ctypes.POINTER(TimeParams), _vp, _vp, _vp, _vp]),
+    "mtg_ragged_time_optimize": (ctypes.c_int, [_vp, ctypes.c_int64, _vp, _vp, _vp,
+                                                ctypes.POINTER(TimeParams), ctypes.c_int, _vp,
+                                                _vp, _vp, _vp, _vp, _vp]),
     "mtg_tube_num_constraints": (ctypes.c_int, [ctypes.c_int, ctypes.c_int]),
     "mtg_tube_residuals": (ctypes.c_int, [_vp, ctypes.c_int, ctypes.c_int, ctypes.c_int,
                                           ctypes.c_int64, _vp, _vp, _vp, _vp, _vp, _vp, _vp,

@@ -484,6 +484,156 @@ def _abi_numeric():
     return -5  # MTG_ERR_NUMERIC: per-trajectory status carries the detail
 
 
+def _require_counts(t, B):
+    import torch
+    if not isinstance(t, torch.Tensor) or not t.is_cuda:
+        raise MTGError("seg_counts must be a CUDA tensor")
+    if t.dtype != torch.int32:
+        raise MTGError("seg_counts must be int32")
+    if tuple(t.shape) != (B,):
+        raise MTGError(f"seg_counts has shape {tuple(t.shape)}, expected {(B,)}")
+    if not t.is_contiguous():
+        raise MTGError("seg_counts must be contiguous")
+
+
+class RaggedLinearPlan:
+    """(N, D, r, S_max) -> batched solves of standard-pattern trajectories
+    with per-trajectory segment counts in one launch (mtg_ragged_plan_create).
+
+    Every array is a padded rectangle (include/mtg_hip.h, "Ragged batches"):
+    seg_counts [B] int32, fixed_vals [B, D, nf_max], times [B, S_max]; see
+    pack_ragged.  The counts stay on the device: no method reads them."""
+
+    def __init__(self, ctx, N, D, r, S_max):
+        self.N, self.D, self.r, self.S_max = N, D, r, S_max
+        self._h = ctypes.c_void_p()
+        check(lib().mtg_ragged_plan_create(ctx.handle, N, D, r, S_max, ctypes.byref(self._h)),
+              "mtg_ragged_plan_create")
+        nf, np_ = ctypes.c_int(), ctypes.c_int()
+        check(lib().mtg_ragged_plan_counts(self._h, ctypes.byref(nf), ctypes.byref(np_)),
+              "mtg_ragged_plan_counts")
+        self.nf_max, self.np_max = nf.value, np_.value
+
+    def close(self):
+        if self._h:
+            lib().mtg_ragged_plan_destroy(self._h)
+            self._h = ctypes.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def _inputs(self, seg_counts, fixed_vals, times):
+        B = times.shape[0]
+        _require(times, (B, self.S_max), "times")
+        _require(fixed_vals, (B, self.D, self.nf_max), "fixed_vals")
+        _require_counts(seg_counts, B)
+        return B
+
+    def solve(self, seg_counts, fixed_vals, times, cost=True, free=False, status=True, out=None):
+        """Batched solveLinear + computeCost (mtg_ragged_linear_solve).
+        Returns a dict with coeffs [B, S_max, D, N] (segments >= S_b are 0.0)
+        and optionally cost [B], free [B, D, np_max] (0.0 past each row's
+        (S_b - 1)(N/2 - 1) entries), status [B] (int32)."""
+        import torch
+        B = self._inputs(seg_counts, fixed_vals, times)
+        dev = times.device
+        o = out or {}
+        if "coeffs" not in o:
+            o["coeffs"] = torch.empty((B, self.S_max, self.D, self.N), dtype=torch.float64,
+                                      device=dev)
+        if cost and "cost" not in o:
+            o["cost"] = torch.empty(B, dtype=torch.float64, device=dev)
+        if free and "free" not in o:
+            o["free"] = torch.empty((B, self.D, self.np_max), dtype=torch.float64, device=dev)
+        if status and "status" not in o:
+            o["status"] = torch.empty(B, dtype=torch.int32, device=dev)
+        _require(o["coeffs"], (B, self.S_max, self.D, self.N), "coeffs")
+        check(lib().mtg_ragged_linear_solve(self._h, B, _ptr(seg_counts), _ptr(fixed_vals),
+                                            _ptr(times), _ptr(o["coeffs"]), _ptr(o.get("cost")),
+                                            _ptr(o.get("free")), _ptr(o.get("status")),
+                                            _stream(dev)), "mtg_ragged_linear_solve")
+        return o
+
+    def time_cost(self, seg_counts, fixed_vals, times, time_penalty=500.0, grad_mode=0,
+                  increment=0.1, w_d=0.1, w_t=1.0, soft=None, soft_weight=100.0, hard=False,
+                  hard_tolerance=0.1):
+        """objectiveFunctionTime per trajectory (mtg_ragged_time_cost); rows
+        need S_b >= 2; grad [B, S_max] is 0.0 past S_b.  Soft and hard
+        constraints are not supported on ragged batches (MTGError)."""
+        import torch
+        B = self._inputs(seg_counts, fixed_vals, times)
+        dev = times.device
+        cost = torch.empty(B, dtype=torch.float64, device=dev)
+        grad = (torch.empty((B, self.S_max), dtype=torch.float64, device=dev)
+                if grad_mode else None)
+        status = torch.empty(B, dtype=torch.int32, device=dev)
+        p = make_time_params(time_penalty, increment, w_d, w_t, grad_mode, soft, soft_weight,
+                             hard=hard, hard_tolerance=hard_tolerance)
+        check(lib().mtg_ragged_time_cost(self._h, B, _ptr(seg_counts), _ptr(fixed_vals),
+                                         _ptr(times), ctypes.byref(p), _ptr(cost), _ptr(grad),
+                                         _ptr(status), _stream(dev)), "mtg_ragged_time_cost")
+        return dict(cost=cost, grad=grad, status=status)
+
+    def time_optimize(self, seg_counts, fixed_vals, times, max_evals=50, time_penalty=500.0,
+                      increment=0.1, w_d=0.1, w_t=1.0, soft=None, soft_weight=100.0, hard=False,
+                      hard_tolerance=0.1, optimizer="fd", f_rel=0.05, f_abs=-1.0,
+                      initial_stepsize_rel=0.1):
+        """Optimise segment times on a copy (mtg_ragged_time_optimize); returns
+        dict(times, cost, evals, solves, result, status) as
+        LinearPlan.time_optimize.  times entries past S_b keep their input
+        bits; a row with S_b < 2 keeps all of them."""
+        import torch
+        B = self._inputs(seg_counts, fixed_vals, times)
+        dev = times.device
+        t = times.clone()
+        cost = torch.empty(B, dtype=torch.float64, device=dev)
+        evals = torch.empty(B, dtype=torch.int32, device=dev)
+        solves = torch.empty(B, dtype=torch.int32, device=dev)
+        result = torch.empty(B, dtype=torch.int32, device=dev)
+        status = torch.empty(B, dtype=torch.int32, device=dev)
+        p = make_time_params(time_penalty, increment, w_d, w_t, 2, soft, soft_weight,
+                             hard=hard, hard_tolerance=hard_tolerance, optimizer=optimizer,
+                             f_rel=f_rel, f_abs=f_abs, initial_stepsize_rel=initial_stepsize_rel)
+        check(lib().mtg_ragged_time_optimize(self._h, B, _ptr(seg_counts), _ptr(fixed_vals),
+                                             _ptr(t), ctypes.byref(p), max_evals, _ptr(cost),
+                                             _ptr(evals), _ptr(solves), _ptr(result),
+                                             _ptr(status), _stream(dev)),
+              "mtg_ragged_time_optimize")
+        return dict(times=t, cost=cost, evals=evals, solves=solves, result=result,
+                    status=status)
+
+
+def pack_ragged(problems, N, device, S_max=None):
+    """Padded inputs of RaggedLinearPlan from a list of (d_f [D, nf_b],
+    times [S_b]) with nf_b = N + S_b - 1 (the order of LinearPlan.solve's
+    fixed_vals).  Returns seg_counts [B] int32, fixed_vals [B, D, nf_max],
+    times [B, S_max] on `device` (S_max None: the longest count).  The padding of
+    both float arrays is NaN: no kernel may read it, and one that does shows."""
+    import torch
+    if not problems:
+        raise MTGError("pack_ragged needs at least one problem")
+    probs = [(np.asarray(df, dtype=np.float64), np.asarray(t, dtype=np.float64).reshape(-1))
+             for df, t in problems]
+    D = probs[0][0].shape[0]
+    counts = np.array([t.size for _, t in probs], dtype=np.int32)
+    S_max = int(counts.max()) if S_max is None else int(S_max)
+    if S_max < int(counts.max()):
+        raise MTGError(f"S_max = {S_max} is below the longest count {int(counts.max())}")
+    fixed = np.full((len(probs), D, N + S_max - 1), np.nan)
+    times = np.full((len(probs), S_max), np.nan)
+    for b, (df, t) in enumerate(probs):
+        if t.size < 1 or df.shape != (D, N + t.size - 1):
+            raise MTGError(f"problem {b}: d_f has shape {df.shape}, expected "
+                           f"{(D, N + t.size - 1)} for {t.size} segments")
+        fixed[b, :, :df.shape[1]] = df
+        times[b, :t.size] = t
+    return (torch.from_numpy(counts).to(device), torch.from_numpy(fixed).to(device),
+            torch.from_numpy(times).to(device))
+
+
 def segment_matrices(ctx, N, r, times):
     """Q, A, A^-1, H for each time in a CUDA float64 tensor [n] -> 4 x [n, N, N]."""
     import torch

@@ -55,6 +55,14 @@ struct mtg_plan {
   std::unique_ptr<mtg_staging> stage{new mtg_staging};
 };
 
+// A ragged plan (mtg_ragged_plan_create) owns nothing on the device: the
+// table belongs to the context's cache.  The device id is a copy, so no call
+// on the plan dereferences the context.
+struct mtg_ragged_plan {
+  int device = 0;
+  mtg::RaggedDev dev{};
+};
+
 namespace {
 
 using mtg::PlanDev;
@@ -906,6 +914,104 @@ int mtg_time_optimize(const mtg_plan* plan, int64_t B, const double* fixed_vals,
                       void* stream) {
   return mtg_time_optimize_ex(plan, B, fixed_vals, times_io, params, max_evals, cost, evals,
                               solves, nullptr, status, stream);
+}
+
+int mtg_ragged_plan_create(mtg_ctx* ctx, int N, int D, int r, int S_max,
+                           mtg_ragged_plan** out) {
+  if (!out) return MTG_ERR_INVALID_ARG;
+  *out = nullptr;
+  // the sizes first: they need no context
+  if (!valid_N(N) || D < 1 || D > mtg::kMaxD || r < 0 || r > N / 2 - 1 || S_max < 1)
+    return MTG_ERR_INVALID_ARG;
+  if (S_max > mtg::kMaxStdS ||
+      mtg::ragged_linear_lds_bytes(N, S_max, D) > static_cast<size_t>(mtg::kMaxLdsBytes))
+    return MTG_ERR_UNSUPPORTED;
+  if (!ctx) return MTG_ERR_INVALID_ARG;
+  const double* tab = nullptr;
+  const int rc = get_tables(ctx, N, r, &tab);
+  if (rc) return rc;
+  mtg_ragged_plan* p = new mtg_ragged_plan;
+  p->device = ctx->device;
+  p->dev = mtg::RaggedDev{N, D, r, S_max, tab};
+  *out = p;
+  return MTG_OK;
+}
+
+int mtg_ragged_plan_destroy(mtg_ragged_plan* plan) {
+  if (!plan) return MTG_ERR_INVALID_ARG;
+  delete plan;
+  return MTG_OK;
+}
+
+int mtg_ragged_plan_counts(const mtg_ragged_plan* plan, int* nf_max, int* np_max) {
+  if (!plan) return MTG_ERR_INVALID_ARG;
+  const int M = plan->dev.N / 2;
+  if (nf_max) *nf_max = 2 * M + plan->dev.S_max - 1;
+  if (np_max) *np_max = (plan->dev.S_max - 1) * (M - 1);
+  return MTG_OK;
+}
+
+int mtg_ragged_linear_solve(const mtg_ragged_plan* plan, int64_t B, const int32_t* seg_counts,
+                            const double* fixed_vals, const double* times, double* coeffs,
+                            double* cost, double* free_vals, int32_t* status, void* stream) {
+  clear_stale_error();
+  if (!plan || B < 0 || B > 0x7fffffff || !seg_counts || !fixed_vals || !times || !coeffs)
+    return MTG_ERR_INVALID_ARG;
+  if (B == 0) return MTG_OK;
+  return from_hip(mtg::launch_ragged_linear_solve(plan->dev, B, seg_counts, fixed_vals, times,
+                                                  coeffs, cost, free_vals, status,
+                                                  static_cast<hipStream_t>(stream)));
+}
+
+// The ragged time entries: the coverage of the runtime-S standard time
+// kernels without soft or hard constraints, and the LDS for S_max checked
+// here, not met as a failure of the launch.
+static int ragged_time_check(const mtg_ragged_plan* plan, const mtg_time_params* p,
+                             bool optimiser) {
+  if (p->n_soft < 0 || p->n_soft > mtg::kMaxSoftConstraints) return MTG_ERR_INVALID_ARG;
+  if (p->n_soft > 0 || p->hard_constraints != 0) return MTG_ERR_UNSUPPORTED;
+  if (!mtg::has_ragged_time(plan->dev)) return MTG_ERR_UNSUPPORTED;
+  if (mtg::ragged_time_lds_bytes(plan->dev.N, plan->dev.S_max, plan->dev.D, optimiser) >
+      static_cast<size_t>(mtg::kMaxLdsBytes))
+    return MTG_ERR_UNSUPPORTED;
+  return MTG_OK;
+}
+
+int mtg_ragged_time_cost(const mtg_ragged_plan* plan, int64_t B, const int32_t* seg_counts,
+                         const double* fixed_vals, const double* times,
+                         const mtg_time_params* params, double* cost, double* grad,
+                         int32_t* status, void* stream) {
+  clear_stale_error();
+  if (!plan || !params || B < 0 || B > 0x7fffffff || !seg_counts || !fixed_vals || !times)
+    return MTG_ERR_INVALID_ARG;
+  if (params->grad_mode < 0 || params->grad_mode > 2) return MTG_ERR_INVALID_ARG;
+  if (params->grad_mode && !(params->increment > 0)) return MTG_ERR_INVALID_ARG;
+  const int rc = ragged_time_check(plan, params, false);
+  if (rc) return rc;
+  if (B == 0) return MTG_OK;
+  return from_hip(mtg::launch_ragged_time_cost(plan->dev, B, seg_counts, fixed_vals, times,
+                                               *params, cost, grad, status,
+                                               static_cast<hipStream_t>(stream)));
+}
+
+int mtg_ragged_time_optimize(const mtg_ragged_plan* plan, int64_t B, const int32_t* seg_counts,
+                             const double* fixed_vals, double* times_io,
+                             const mtg_time_params* params, int max_evals, double* cost,
+                             int32_t* evals, int32_t* solves, int32_t* result, int32_t* status,
+                             void* stream) {
+  clear_stale_error();
+  if (!plan || !params || B < 0 || B > 0x7fffffff || !seg_counts || !fixed_vals || !times_io ||
+      max_evals < 1)
+    return MTG_ERR_INVALID_ARG;
+  if (!(params->increment > 0)) return MTG_ERR_INVALID_ARG;
+  if (params->optimizer != 0 && params->optimizer != 1) return MTG_ERR_INVALID_ARG;
+  const int rc = ragged_time_check(plan, params, true);
+  if (rc) return rc;
+  if (B == 0) return MTG_OK;
+  return from_hip(mtg::launch_ragged_time_optimize(plan->dev, B, seg_counts, fixed_vals,
+                                                   times_io, *params, max_evals, cost, evals,
+                                                   solves, result, status,
+                                                   static_cast<hipStream_t>(stream)));
 }
 
 int mtg_tube_num_constraints(int N, int S) {

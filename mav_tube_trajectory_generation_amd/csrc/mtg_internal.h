@@ -102,6 +102,32 @@ hipError_t launch_time_optimize_std(const PlanDev& pl, int64_t B, const double* 
                                     int32_t* result, int32_t* status, hipStream_t st);
 size_t time_std_lds_bytes(int N, int S, int D, bool soft);
 
+// Ragged batches of the standard pattern (mtg_ragged.hip): per-trajectory
+// segment counts (device) in rows padded to S_max.  Device view of a
+// mtg_ragged_plan.
+struct RaggedDev {
+  int N, D, r, S_max;
+  const double* tab;  // H(1) then A(1)^-1, N*N each (device)
+};
+hipError_t launch_ragged_linear_solve(const RaggedDev& pl, int64_t B, const int32_t* seg_counts,
+                                      const double* df, const double* times, double* coeffs,
+                                      double* cost, double* free_vals, int32_t* status,
+                                      hipStream_t st);
+// N = 10, r = 2..4, D = 1..3, as has_time_std.
+bool has_ragged_time(const RaggedDev& pl);
+hipError_t launch_ragged_time_cost(const RaggedDev& pl, int64_t B, const int32_t* seg_counts,
+                                   const double* df, const double* times,
+                                   const mtg_time_params& p, double* cost, double* grad,
+                                   int32_t* status, hipStream_t st);
+hipError_t launch_ragged_time_optimize(const RaggedDev& pl, int64_t B, const int32_t* seg_counts,
+                                       const double* df, double* times,
+                                       const mtg_time_params& p, int max_evals, double* cost,
+                                       int32_t* evals, int32_t* solves, int32_t* result,
+                                       int32_t* status, hipStream_t st);
+// LDS per workgroup: sized by S_max, whatever the trajectory's own count.
+size_t ragged_linear_lds_bytes(int N, int S_max, int D);
+size_t ragged_time_lds_bytes(int N, int S_max, int D, bool optimiser);
+
 // Free-derivative objectives and optimiser (mtg_free.hip).
 hipError_t launch_free_cost(const PlanDev& pl, int64_t B, const double* df, const double* dp,
                             const double* times, const mtg_time_params& p, int mode,

@@ -259,7 +259,7 @@ __global__ __launch_bounds__(kWave) void time_cost_kernel(
   const int64_t b = blockIdx.x;
   double* cbuf = reinterpret_cast<double*>(reinterpret_cast<char*>(smem) + soft_cbuf_offset(lay));
   ev.load_inputs(pl.tab, pl.slots, pl.fixed_map, times + b * S, fixed_vals + b * D * nf, nf);
-  time_cost_drive(ev, S, pl.tab, cbuf, times, p, cost, grad, status);
+  time_cost_drive(ev, S, S, pl.tab, cbuf, times, p, cost, grad, status);
 }
 
 template <int N, bool kSoft>
@@ -278,7 +278,7 @@ __global__ __launch_bounds__(kWave) void time_optimize_kernel(
   auto* sbs = reinterpret_cast<sbplx::State*>(reinterpret_cast<char*>(smem) +
                                               sbplx_state_offset(lay, S, D, N, kSoft));
   ev.load_inputs(pl.tab, pl.slots, pl.fixed_map, times_io + b * S, fixed_vals + b * D * nf, nf);
-  time_optimize_drive(ev, S, pl.tab, cbuf, times_io, p, max_evals, cost, evals_out, solves_out,
+  time_optimize_drive(ev, S, S, pl.tab, cbuf, times_io, p, max_evals, cost, evals_out, solves_out,
                       result_out, status, sbs);
 }
 

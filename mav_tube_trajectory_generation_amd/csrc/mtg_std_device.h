@@ -2,8 +2,9 @@
 // pattern (start and end vertex fully fixed, intermediate vertices position
 // only: createRandomVertices / makeStartOrEnd, vertex.cpp:27-82, 147-153),
 // run by one 64-lane wavefront (one workgroup).  Used by the standard-pattern
-// linear-solve kernel (mtg_linear_std.hip) and the standard-pattern
-// time-allocation kernels (mtg_time_std.hip).
+// linear-solve kernel (mtg_linear_std.hip), the standard-pattern
+// time-allocation kernels (mtg_time_std.hip) and the ragged-batch kernels
+// (mtg_ragged.hip: S per trajectory; the phases below need S >= 2).
 //
 // Same mathematics as the generic solver (mtg_device.h: linear_impl:277-379,
 // 254-275, 113-130 restated with the exact time scaling

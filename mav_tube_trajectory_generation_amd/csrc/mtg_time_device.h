@@ -22,6 +22,9 @@
 //                         double* g, double* scratch);
 //                       the grad_mode 1 gradient at the base times Tb, d held
 //                       at the base solution, into g (S); scratch: 2S doubles.
+// The global rows of trajectory b (times, grad, times_io) start at
+// b * row_stride: S for the uniform kernels, S_max for the ragged ones
+// (mtg_ragged.hip), whose rows are padded rectangles.
 // Each driver calls eval from ONE call site (a loop over evaluation points),
 // so the solver body is instantiated once per kernel and stays within the
 // register file.  The hooks are always_inline and the evaluator is the
@@ -64,7 +67,7 @@ __device__ __attribute__((always_inline)) inline int traj_status(bool bad, bool 
 // T_n > 0.1), makes the row MTG_TRAJ_BAD_TIME with NaN cost and gradient.
 template <class Ev>
 __device__ __attribute__((always_inline)) void time_cost_drive(
-    Ev& ev, int S, const double* __restrict__ tab, double* cbuf,
+    Ev& ev, int S, int row_stride, const double* __restrict__ tab, double* cbuf,
     const double* __restrict__ times, const mtg_time_params& p, double* __restrict__ cost,
     double* __restrict__ grad, int32_t* __restrict__ status) {
   const int64_t b = blockIdx.x;
@@ -72,7 +75,7 @@ __device__ __attribute__((always_inline)) void time_cost_drive(
   double* T = ev.T();        // evaluation point
   double* Tb = ev.state(S);  // base times
   double* g = Tb + S;        // gradient, then 2S doubles for the grad_mode 1 hook
-  for (int i = lane; i < S; i += kWave) T[i] = Tb[i] = times[b * S + i];
+  for (int i = lane; i < S; i += kWave) T[i] = Tb[i] = times[b * row_stride + i];
   const bool fd = grad && p.grad_mode == 2;
   const int nevals = 1 + (fd ? 2 * S : 0);
   double J0 = 0.0, Jlo = 0.0;
@@ -97,7 +100,7 @@ __device__ __attribute__((always_inline)) void time_cost_drive(
     if (status) status[b] = traj_status(bad, ev.not_spd());
   }
   if (grad && p.grad_mode != 0)
-    for (int i = lane; i < S; i += kWave) grad[b * S + i] = bad ? NAN : g[i];
+    for (int i = lane; i < S; i += kWave) grad[b * row_stride + i] = bad ? NAN : g[i];
 }
 
 // Bounds [0.1, 2 T0]; p.optimizer 0: projected, scaled steepest descent on
@@ -108,8 +111,8 @@ __device__ __attribute__((always_inline)) void time_cost_drive(
 // evaluation per loop trip.
 template <class Ev>
 __device__ __attribute__((always_inline)) void time_optimize_drive(
-    Ev& ev, int S, const double* __restrict__ tab, double* cbuf, double* __restrict__ times_io,
-    const mtg_time_params& p, int max_evals, double* __restrict__ cost,
+    Ev& ev, int S, int row_stride, const double* __restrict__ tab, double* cbuf,
+    double* __restrict__ times_io, const mtg_time_params& p, int max_evals, double* __restrict__ cost,
     int32_t* __restrict__ evals_out, int32_t* __restrict__ solves_out,
     int32_t* __restrict__ result_out, int32_t* __restrict__ status, sbplx::State* sbs) {
   const int64_t b = blockIdx.x;
@@ -119,7 +122,7 @@ __device__ __attribute__((always_inline)) void time_optimize_drive(
   double* T0 = Tcur + S;      // initial times (bounds)
   double* g = T0 + S;         // gradient at Tcur
   double* gv = g + S;         // gradient of the violation at Tcur (hard constraints)
-  for (int i = lane; i < S; i += kWave) T[i] = Tcur[i] = T0[i] = times_io[b * S + i];
+  for (int i = lane; i < S; i += kWave) T[i] = Tcur[i] = T0[i] = times_io[b * row_stride + i];
   constexpr double kLower = 0.1;  // kOptimizationTimeLowerBound (:370)
   enum { kBase, kGrad, kTrial, kDone };
   int phase = kBase, gi = 0, evals = 0, nsolve = 0, res = 0;
@@ -217,7 +220,7 @@ __device__ __attribute__((always_inline)) void time_optimize_drive(
   } else {
     res = evals >= max_evals ? sbplx::kMaxEval : sbplx::kXtol;
   }
-  for (int i = lane; i < S; i += kWave) times_io[b * S + i] = Tcur[i];
+  for (int i = lane; i < S; i += kWave) times_io[b * row_stride + i] = Tcur[i];
   const bool bad = ev.bad();
   if (lane == 0) {
     if (cost) cost[b] = bad ? NAN : f;
