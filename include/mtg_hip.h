@@ -363,6 +363,77 @@ int mtg_ragged_time_optimize(const mtg_ragged_plan* plan, int64_t B, const int32
                              void* stream);
 
 /* ------------------------------------------------------------------------
+ * Ragged evaluators: mtg_max_magnitude, mtg_soft_constraint_cost and
+ * mtg_sample_trajectories over the arrays a ragged solve writes, in one
+ * launch each.  Plan-free, like their uniform counterparts (documented
+ * further down: the candidate rules, the cost formula and evaluateRange's
+ * sampling rule are theirs).  Per row b the result is exactly what the
+ * uniform entry point gives for coeffs[b, :S_b], times[b, :S_b]: candidates
+ * in segment order, the first maximum wins (strict '>' from Extremum() =
+ * {0, 0, 0}); cost_b = sum_c min(maximum_cost, exp((max_bc - limit_c) /
+ * limit_c * weight)); t_end < 0 means the row's own total time
+ * sum_{s < S_b} T_s.
+ *
+ * Layout (device):
+ *   seg_counts  B                  int32, 1 <= S_b <= S_max, read by the
+ *                                  kernels only: the host never sees the
+ *                                  counts, so a captured launch may be
+ *                                  replayed over other counts
+ *   coeffs      B x S_max x D x N  the first S_b segments are read; the rest
+ *                                  is never read (mtg_ragged_linear_solve
+ *                                  writes 0.0 there; NaN does no harm)
+ *   times       B x S_max          the first S_b are read; the rest is never
+ *                                  read (and may be NaN)
+ * Outputs are shaped as in the uniform calls: max_time, max_value,
+ * max_segment B (each nullable); maxima B x n_constraints, cost B; samples
+ * B x ((max_derivative+1) * D) x n_max channel-major, sample_times B x n_max
+ * (nullable), n_samples B (nullable).
+ *
+ * A row whose count is outside [1, S_max] touches nothing outside its own
+ * row.  Its outputs: max_value, max_time, cost and every maxima[b, :] NaN;
+ * max_segment[b] -1; gate_out[b] +inf; n_samples[b] -1, and none of its
+ * samples or sample times is written.
+ *
+ * Feasibility gate of mtg_ragged_soft_constraint_cost: gate_in and gate_out
+ * (device, B; typically the solve's cost) are both nullable; with gate_out
+ * NULL nothing is written (gate_out without gate_in is invalid).
+ *   gate_out[b] = gate_in[b]  if maxima[b, c] <= limits[c] for every c,
+ *                 +inf        otherwise.
+ * A NaN gate_in passes through; gate_out may alias gate_in.
+ * mtg_select_local lets NaN and +inf lose, so ragged solve -> this call ->
+ * mtg_select_local picks the cheapest feasible row with no host step.
+ *
+ * Arguments as in the uniform calls: N in {4, 6, 8, 10, 12}, D <= 4,
+ * 0 <= derivative <= 4 and derivative <= N - 2, 1 <= n_constraints <= 8
+ * (derivatives and limits are HOST arrays), dt > 0, t_start >= 0, B <= 65535
+ * for sampling.  1 <= S_max <= 64 (MTG_ERR_INVALID_ARG below 1,
+ * MTG_ERR_UNSUPPORTED above 64, both before any pointer is looked at).
+ * NULL seg_counts, coeffs or times with B > 0 is MTG_ERR_INVALID_ARG; B == 0
+ * returns MTG_OK and launches nothing.  The kernels' LDS, sized by S_max, is
+ * checked here (MTG_ERR_UNSUPPORTED), never met as a failed launch.
+ *
+ * Extrema: one workgroup of up to four waves per trajectory; every segment
+ * is searched in 8 parts whatever S_b (a wave takes several passes where
+ * S_b * 8 items exceed the workgroup).  Sampling: 1024 samples per
+ * workgroup, as mtg_sample_trajectories.
+ */
+int mtg_ragged_max_magnitude(int N, int D, int S_max, int64_t B, const int32_t* seg_counts,
+                             const double* coeffs, const double* times, int derivative,
+                             double* max_time, double* max_value, int32_t* max_segment,
+                             void* stream);
+int mtg_ragged_soft_constraint_cost(int N, int D, int S_max, int64_t B, const int32_t* seg_counts,
+                                    const double* coeffs, const double* times,
+                                    int n_constraints, const int* derivatives, const double* limits,
+                                    double weight, double maximum_cost,
+                                    double* maxima, double* cost,
+                                    const double* gate_in, double* gate_out, void* stream);
+int mtg_ragged_sample_trajectories(int N, int D, int S_max, int64_t B, const int32_t* seg_counts,
+                                   const double* coeffs, const double* times, double t_start,
+                                   double t_end, double dt, int n_max, int max_derivative,
+                                   double* samples, double* sample_times, int32_t* n_samples,
+                                   void* stream);
+
+/* ------------------------------------------------------------------------
  * Free-derivative objectives of PolynomialOptimizationNonLinear (the NLopt
  * callbacks of kOptimizeFreeConstraints / kOptimizeFreeConstraintsAndTime),
  * for any constraint pattern of the plan (the fork's nonlinear class uses the

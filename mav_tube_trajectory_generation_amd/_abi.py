@@ -215,6 +215,19 @@ SIGNATURES = {
     "mtg_ragged_time_optimize": (ctypes.c_int, [_vp, ctypes.c_int64, _vp, _vp, _vp,
                                                 ctypes.POINTER(TimeParams), ctypes.c_int, _vp,
                                                 _vp, _vp, _vp, _vp, _vp]),
+    "mtg_ragged_max_magnitude": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                                                ctypes.c_int64, _vp, _vp, _vp, ctypes.c_int, _vp,
+                                                _vp, _vp, _vp]),
+    "mtg_ragged_soft_constraint_cost": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                                                       ctypes.c_int64, _vp, _vp, _vp,
+                                                       ctypes.c_int, ctypes.POINTER(ctypes.c_int),
+                                                       _dp, ctypes.c_double, ctypes.c_double,
+                                                       _vp, _vp, _vp, _vp, _vp]),
+    "mtg_ragged_sample_trajectories": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                                                      ctypes.c_int64, _vp, _vp, _vp,
+                                                      ctypes.c_double, ctypes.c_double,
+                                                      ctypes.c_double, ctypes.c_int, ctypes.c_int,
+                                                      _vp, _vp, _vp, _vp]),
     "mtg_tube_num_constraints": (ctypes.c_int, [ctypes.c_int, ctypes.c_int]),
     "mtg_tube_residuals": (ctypes.c_int, [_vp, ctypes.c_int, ctypes.c_int, ctypes.c_int,
                                           ctypes.c_int64, _vp, _vp, _vp, _vp, _vp, _vp, _vp,

@@ -634,6 +634,121 @@ def pack_ragged(problems, N, device, S_max=None):
             torch.from_numpy(times).to(device))
 
 
+def _ragged_eval_inputs(seg_counts, coeffs, times):
+    import torch
+    if not isinstance(coeffs, torch.Tensor) or coeffs.dim() != 4:
+        raise MTGError("coeffs must be a CUDA tensor [B, S_max, D, N]")
+    B, S_max, D, N = coeffs.shape
+    _require(coeffs, (B, S_max, D, N), "coeffs")
+    _require(times, (B, S_max), "times")
+    _require_counts(seg_counts, B)
+    return B, S_max, D, N
+
+
+def ragged_max_magnitude(seg_counts, coeffs, times, derivative, out=None):
+    """max_magnitude over a ragged batch in one launch
+    (mtg_ragged_max_magnitude): row b is the Extremum of |p^(derivative)| over
+    coeffs[b, :S_b], times[b, :S_b], S_b = seg_counts[b].
+
+    seg_counts [B] int32, coeffs [B, S_max, D, N], times [B, S_max] (CUDA), as
+    RaggedLinearPlan.solve and pack_ragged give them; the padding is never
+    read.  Returns a dict of time [B], value [B], segment [B] int32.  A row
+    whose count is outside [1, S_max] gets NaN, NaN, -1.  The counts stay on
+    the device."""
+    import torch
+    B, S_max, D, N = _ragged_eval_inputs(seg_counts, coeffs, times)
+    dev = times.device
+    if out is None:
+        out = {"time": torch.empty(B, dtype=torch.float64, device=dev),
+               "value": torch.empty(B, dtype=torch.float64, device=dev),
+               "segment": torch.empty(B, dtype=torch.int32, device=dev)}
+    check(lib().mtg_ragged_max_magnitude(N, D, S_max, B, _ptr(seg_counts), _ptr(coeffs),
+                                         _ptr(times), derivative, _ptr(out["time"]),
+                                         _ptr(out["value"]), _ptr(out["segment"]), _stream(dev)),
+          "mtg_ragged_max_magnitude")
+    return out
+
+
+def ragged_soft_constraint_cost(seg_counts, coeffs, times, derivatives, limits, weight=100.0,
+                                maximum_cost=1.0e12, gate=None, out=None):
+    """soft_constraint_cost over a ragged batch in one launch
+    (mtg_ragged_soft_constraint_cost), inputs as ragged_max_magnitude.
+
+    Returns a dict of cost [B] and maxima [B, n_constraints]; with gate [B]
+    (typically the solve's cost) also gated [B]: gate[b] where every
+    maxima[b, c] <= limits[c], +inf elsewhere (a NaN gate passes through), so
+    a selection over gated picks the cheapest feasible row.  out["gated"] may
+    be gate itself.  A row whose count is outside [1, S_max] gets NaN cost and
+    maxima and gated +inf."""
+    import torch
+    B, S_max, D, N = _ragged_eval_inputs(seg_counts, coeffs, times)
+    nc = len(derivatives)
+    if len(limits) != nc:
+        raise MTGError("derivatives and limits differ in length")
+    if gate is not None:
+        _require(gate, (B,), "gate")
+    dev = times.device
+    out = dict(out) if out is not None else {}
+    if "cost" not in out:
+        out["cost"] = torch.empty(B, dtype=torch.float64, device=dev)
+    if "maxima" not in out:
+        out["maxima"] = torch.empty((B, nc), dtype=torch.float64, device=dev)
+    _require(out["cost"], (B,), "cost")
+    _require(out["maxima"], (B, nc), "maxima")
+    if gate is not None:
+        if "gated" not in out:
+            out["gated"] = torch.empty(B, dtype=torch.float64, device=dev)
+        _require(out["gated"], (B,), "gated")
+    der = (ctypes.c_int * max(nc, 1))(*[int(d) for d in derivatives])
+    lim = (ctypes.c_double * max(nc, 1))(*[float(v) for v in limits])
+    check(lib().mtg_ragged_soft_constraint_cost(
+        N, D, S_max, B, _ptr(seg_counts), _ptr(coeffs), _ptr(times), nc, der, lim, float(weight),
+        float(maximum_cost), _ptr(out["maxima"]), _ptr(out["cost"]), _ptr(gate),
+        _ptr(out["gated"] if gate is not None else None), _stream(dev)),
+        "mtg_ragged_soft_constraint_cost")
+    return out
+
+
+def ragged_sample_trajectories(seg_counts, coeffs, times, dt, t_start=0.0, t_end=-1.0,
+                               max_derivative=0, n_max=None, with_times=True):
+    """sample_trajectories over a ragged batch in one launch
+    (mtg_ragged_sample_trajectories), inputs as ragged_max_magnitude; t_end < 0
+    means each row's own total time.
+
+    Returns (samples [B, (max_derivative+1)*D, n_max] channel-major,
+    sample_times [B, n_max] or None, n_samples [B] int32).  A row whose count
+    is outside [1, S_max] gets n_samples -1 and no samples.
+
+    The default n_max is the longest row's sample count, from the row sums of
+    times masked by the counts: that default is the one place a ragged call
+    reads the counts on the host (a device-to-host copy and a
+    synchronisation).  Pass n_max to keep the call free of host reads, e.g.
+    under graph capture."""
+    import torch
+    B, S_max, D, N = _ragged_eval_inputs(seg_counts, coeffs, times)
+    dev = times.device
+    if not dt > 0:
+        raise MTGError("dt must be > 0")
+    if n_max is None:
+        if t_end < 0:
+            mask = torch.arange(S_max, device=dev)[None, :] < seg_counts[:, None]
+            span = float(torch.where(mask, times, torch.zeros_like(times)).sum(dim=1).max().item())
+        else:
+            span = t_end
+        n_max = int(span / dt) + 2
+        n_max = (n_max + 63) // 64 * 64  # 512-byte aligned channel rows
+    nch = (max_derivative + 1) * D
+    samples = torch.empty((B, nch, n_max), dtype=torch.float64, device=dev)
+    stimes = torch.empty((B, n_max), dtype=torch.float64, device=dev) if with_times else None
+    count = torch.empty(B, dtype=torch.int32, device=dev)
+    check(lib().mtg_ragged_sample_trajectories(N, D, S_max, B, _ptr(seg_counts), _ptr(coeffs),
+                                               _ptr(times), t_start, t_end, dt, n_max,
+                                               max_derivative, _ptr(samples), _ptr(stimes),
+                                               _ptr(count), _stream(dev)),
+          "mtg_ragged_sample_trajectories")
+    return samples, stimes, count
+
+
 def segment_matrices(ctx, N, r, times):
     """Q, A, A^-1, H for each time in a CUDA float64 tensor [n] -> 4 x [n, N, N]."""
     import torch

@@ -1014,6 +1014,95 @@ int mtg_ragged_time_optimize(const mtg_ragged_plan* plan, int64_t B, const int32
                                                    static_cast<hipStream_t>(stream)));
 }
 
+// The ragged evaluators are plan-free: the sizes first (they need neither a
+// pointer nor a device), S_max as mtg_ragged_plan_create takes it.
+static int ragged_eval_sizes(int N, int D, int S_max, int64_t B) {
+  if (!valid_N(N) || D < 1 || D > mtg::kMaxD || S_max < 1 || B < 0) return MTG_ERR_INVALID_ARG;
+  if (S_max > mtg::kMaxStdS) return MTG_ERR_UNSUPPORTED;
+  return MTG_OK;
+}
+
+static bool valid_extrema_derivative(int N, int derivative) {
+  return derivative >= 0 && derivative <= mtg::kMaxExtremaDerivative && N - derivative - 1 > 0;
+}
+
+int mtg_ragged_max_magnitude(int N, int D, int S_max, int64_t B, const int32_t* seg_counts,
+                             const double* coeffs, const double* times, int derivative,
+                             double* max_time, double* max_value, int32_t* max_segment,
+                             void* stream) {
+  clear_stale_error();
+  const int rc = ragged_eval_sizes(N, D, S_max, B);
+  if (rc) return rc;
+  if (!valid_extrema_derivative(N, derivative) || B > 0x7fffffff) return MTG_ERR_INVALID_ARG;
+  if (mtg::ragged_extrema_lds_bytes(N, S_max, D) > static_cast<size_t>(mtg::kMaxLdsBytes))
+    return MTG_ERR_UNSUPPORTED;
+  if (B == 0) return MTG_OK;
+  if (!seg_counts || !coeffs || !times) return MTG_ERR_INVALID_ARG;
+  mtg::SoftSpec spec{};
+  spec.n = 1;
+  spec.derivative[0] = derivative;
+  const mtg::RaggedEvalOut out{max_value, max_time, max_segment, nullptr, nullptr, nullptr};
+  return from_hip(mtg::launch_ragged_extrema(N, D, S_max, B, seg_counts, coeffs, times, spec,
+                                             out, static_cast<hipStream_t>(stream)));
+}
+
+int mtg_ragged_soft_constraint_cost(int N, int D, int S_max, int64_t B, const int32_t* seg_counts,
+                                    const double* coeffs, const double* times,
+                                    int n_constraints, const int* derivatives,
+                                    const double* limits, double weight, double maximum_cost,
+                                    double* maxima, double* cost, const double* gate_in,
+                                    double* gate_out, void* stream) {
+  clear_stale_error();
+  const int rc = ragged_eval_sizes(N, D, S_max, B);
+  if (rc) return rc;
+  if (n_constraints < 1 || n_constraints > mtg::kMaxSoftConstraints || !derivatives || !limits ||
+      B > 0x7fffffff)
+    return MTG_ERR_INVALID_ARG;
+  mtg::SoftSpec spec{};
+  spec.n = n_constraints;
+  spec.weight = weight;
+  spec.maximum_cost = maximum_cost;
+  for (int c = 0; c < n_constraints; ++c) {
+    // addMaximumMagnitudeConstraint: CHECK_GE(derivative, 0), CHECK_GE(value, 0)
+    if (!valid_extrema_derivative(N, derivatives[c]) || !(limits[c] >= 0.0))
+      return MTG_ERR_INVALID_ARG;
+    spec.derivative[c] = derivatives[c];
+    spec.limit[c] = limits[c];
+  }
+  if (mtg::ragged_extrema_lds_bytes(N, S_max, D) > static_cast<size_t>(mtg::kMaxLdsBytes))
+    return MTG_ERR_UNSUPPORTED;
+  if (B == 0) return MTG_OK;
+  if (!seg_counts || !coeffs || !times || !maxima || !cost || (gate_out && !gate_in))
+    return MTG_ERR_INVALID_ARG;
+  const mtg::RaggedEvalOut out{maxima, nullptr, nullptr, cost, gate_in, gate_out};
+  return from_hip(mtg::launch_ragged_extrema(N, D, S_max, B, seg_counts, coeffs, times, spec,
+                                             out, static_cast<hipStream_t>(stream)));
+}
+
+int mtg_ragged_sample_trajectories(int N, int D, int S_max, int64_t B, const int32_t* seg_counts,
+                                   const double* coeffs, const double* times, double t_start,
+                                   double t_end, double dt, int n_max, int max_derivative,
+                                   double* samples, double* sample_times, int32_t* n_samples,
+                                   void* stream) {
+  clear_stale_error();
+  const int rc = ragged_eval_sizes(N, D, S_max, B);
+  if (rc) return rc;
+  if (B > 65535 || n_max < 0 || max_derivative < 0 || max_derivative >= N || !(dt > 0.0) ||
+      !(t_start >= 0.0))
+    return MTG_ERR_INVALID_ARG;
+  if (mtg::ragged_sample_lds_bytes(N, S_max, D, max_derivative) >
+      static_cast<size_t>(mtg::kMaxLdsBytes))
+    return MTG_ERR_UNSUPPORTED;
+  if (B == 0) return MTG_OK;
+  if (!seg_counts || !coeffs || !times) return MTG_ERR_INVALID_ARG;
+  if (n_max == 0) return MTG_OK;
+  if (!samples) return MTG_ERR_INVALID_ARG;
+  return from_hip(mtg::launch_ragged_sample(N, D, S_max, B, seg_counts, coeffs, times, t_start,
+                                            t_end, dt, n_max, max_derivative, samples,
+                                            sample_times, n_samples,
+                                            static_cast<hipStream_t>(stream)));
+}
+
 int mtg_tube_num_constraints(int N, int S) {
   if (!valid_N(N) || S < 1) return MTG_ERR_INVALID_ARG;
   return (S - 1) + S * (N - 2) + 2 * S * (N - 2);

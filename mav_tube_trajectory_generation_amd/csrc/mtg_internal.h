@@ -332,6 +332,30 @@ hipError_t launch_magnitude_candidates(int N, int D, int64_t n_seg, int derivati
                                        double* cand_time, double* cand_value, int32_t* n_cand,
                                        hipStream_t st);
 
+// Evaluators of a ragged batch (mtg_ragged_eval.hip): the extrema, the
+// soft-constraint cost and the sampling of rows padded to S_max, with the
+// counts read on the device.  One extrema kernel serves both the maximum of
+// one derivative (spec.n = 1, cost null) and the soft-constraint cost.
+struct RaggedEvalOut {
+  double* maxima;        // B x spec.n (nullable)
+  double* max_time;      // B: constraint 0's time and segment (nullable)
+  int32_t* max_segment;
+  double* cost;          // B; null: no cost and no gate
+  const double* gate_in;  // B; gate_out = gate_in where every maximum is within
+  double* gate_out;       // its limit, +inf elsewhere (null: no gate; may alias)
+};
+hipError_t launch_ragged_extrema(int N, int D, int S_max, int64_t B, const int32_t* seg_counts,
+                                 const double* coeffs, const double* times, const SoftSpec& spec,
+                                 const RaggedEvalOut& out, hipStream_t st);
+hipError_t launch_ragged_sample(int N, int D, int S_max, int64_t B, const int32_t* seg_counts,
+                                const double* coeffs, const double* times, double t_start,
+                                double t_end, double dt, int n_max, int max_deriv,
+                                double* samples, double* sample_times, int32_t* n_samples,
+                                hipStream_t st);
+// LDS per workgroup, sized by S_max.
+size_t ragged_extrema_lds_bytes(int N, int S_max, int D);
+size_t ragged_sample_lds_bytes(int N, int S_max, int D, int max_deriv);
+
 // Collision-driven objectives and their optimiser (mtg_coll_opt.hip); return
 // MTG_* codes.  All scratch comes from the caller's workspace.
 size_t coll_workspace_bytes(const PlanDev& pl, int64_t B, int mode, const mtg_coll_params& p,
