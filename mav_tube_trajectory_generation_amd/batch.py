@@ -634,6 +634,33 @@ def pack_ragged(problems, N, device, S_max=None):
             torch.from_numpy(times).to(device))
 
 
+def _extremum_out(B, dev):
+    """The Extremum outputs of max_magnitude / ragged_max_magnitude."""
+    import torch
+    return {"time": torch.empty(B, dtype=torch.float64, device=dev),
+            "value": torch.empty(B, dtype=torch.float64, device=dev),
+            "segment": torch.empty(B, dtype=torch.int32, device=dev)}
+
+
+def _sample_outputs(B, D, dev, dt, t_end, max_derivative, n_max, with_times, whole_span):
+    """n_max and the (samples, sample_times or None, n_samples) tuple a sampling
+    call fills and returns.  The default n_max is the sample count of the span
+    t_end, or of whole_span() (the longest trajectory, read on the host) where
+    t_end < 0."""
+    import torch
+    if not dt > 0:
+        raise MTGError("dt must be > 0")
+    if n_max is None:
+        span = float(whole_span()) if t_end < 0 else t_end
+        n_max = int(span / dt) + 2
+        n_max = (n_max + 63) // 64 * 64  # 512-byte aligned channel rows
+    nch = (max_derivative + 1) * D
+    samples = torch.empty((B, nch, n_max), dtype=torch.float64, device=dev)
+    stimes = torch.empty((B, n_max), dtype=torch.float64, device=dev) if with_times else None
+    count = torch.empty(B, dtype=torch.int32, device=dev)
+    return n_max, (samples, stimes, count)
+
+
 def _ragged_eval_inputs(seg_counts, coeffs, times):
     import torch
     if not isinstance(coeffs, torch.Tensor) or coeffs.dim() != 4:
@@ -659,9 +686,7 @@ def ragged_max_magnitude(seg_counts, coeffs, times, derivative, out=None):
     B, S_max, D, N = _ragged_eval_inputs(seg_counts, coeffs, times)
     dev = times.device
     if out is None:
-        out = {"time": torch.empty(B, dtype=torch.float64, device=dev),
-               "value": torch.empty(B, dtype=torch.float64, device=dev),
-               "segment": torch.empty(B, dtype=torch.int32, device=dev)}
+        out = _extremum_out(B, dev)
     check(lib().mtg_ragged_max_magnitude(N, D, S_max, B, _ptr(seg_counts), _ptr(coeffs),
                                          _ptr(times), derivative, _ptr(out["time"]),
                                          _ptr(out["value"]), _ptr(out["segment"]), _stream(dev)),
@@ -727,26 +752,18 @@ def ragged_sample_trajectories(seg_counts, coeffs, times, dt, t_start=0.0, t_end
     import torch
     B, S_max, D, N = _ragged_eval_inputs(seg_counts, coeffs, times)
     dev = times.device
-    if not dt > 0:
-        raise MTGError("dt must be > 0")
-    if n_max is None:
-        if t_end < 0:
-            mask = torch.arange(S_max, device=dev)[None, :] < seg_counts[:, None]
-            span = float(torch.where(mask, times, torch.zeros_like(times)).sum(dim=1).max().item())
-        else:
-            span = t_end
-        n_max = int(span / dt) + 2
-        n_max = (n_max + 63) // 64 * 64  # 512-byte aligned channel rows
-    nch = (max_derivative + 1) * D
-    samples = torch.empty((B, nch, n_max), dtype=torch.float64, device=dev)
-    stimes = torch.empty((B, n_max), dtype=torch.float64, device=dev) if with_times else None
-    count = torch.empty(B, dtype=torch.int32, device=dev)
+
+    def longest_row():
+        mask = torch.arange(S_max, device=dev)[None, :] < seg_counts[:, None]
+        return torch.where(mask, times, torch.zeros_like(times)).sum(dim=1).max().item()
+
+    n_max, res = _sample_outputs(B, D, dev, dt, t_end, max_derivative, n_max, with_times,
+                                 longest_row)
     check(lib().mtg_ragged_sample_trajectories(N, D, S_max, B, _ptr(seg_counts), _ptr(coeffs),
                                                _ptr(times), t_start, t_end, dt, n_max,
-                                               max_derivative, _ptr(samples), _ptr(stimes),
-                                               _ptr(count), _stream(dev)),
+                                               max_derivative, *map(_ptr, res), _stream(dev)),
           "mtg_ragged_sample_trajectories")
-    return samples, stimes, count
+    return res
 
 
 def segment_matrices(ctx, N, r, times):
@@ -918,20 +935,12 @@ def sample_trajectories(coeffs, times, dt, t_start=0.0, t_end=-1.0, max_derivati
     _require(coeffs, (B, S, D, N), "coeffs")
     _require(times, (B, S), "times")
     dev = times.device
-    if not dt > 0:
-        raise MTGError("dt must be > 0")
-    if n_max is None:
-        span = float(times.sum(dim=1).max().item()) if t_end < 0 else t_end
-        n_max = int(span / dt) + 2
-        n_max = (n_max + 63) // 64 * 64  # 512-byte aligned channel rows
-    nch = (max_derivative + 1) * D
-    samples = torch.empty((B, nch, n_max), dtype=torch.float64, device=dev)
-    stimes = torch.empty((B, n_max), dtype=torch.float64, device=dev) if with_times else None
-    count = torch.empty(B, dtype=torch.int32, device=dev)
+    n_max, res = _sample_outputs(B, D, dev, dt, t_end, max_derivative, n_max, with_times,
+                                 lambda: times.sum(dim=1).max().item())
     check(lib().mtg_sample_trajectories(N, D, S, B, _ptr(coeffs), _ptr(times), t_start, t_end,
-                                        dt, n_max, max_derivative, _ptr(samples), _ptr(stimes),
-                                        _ptr(count), _stream(dev)), "mtg_sample_trajectories")
-    return samples, stimes, count
+                                        dt, n_max, max_derivative, *map(_ptr, res), _stream(dev)),
+          "mtg_sample_trajectories")
+    return res
 
 
 def max_magnitude(coeffs, times, derivative, out=None):
@@ -948,9 +957,7 @@ def max_magnitude(coeffs, times, derivative, out=None):
     _require(times, (B, S), "times")
     dev = times.device
     if out is None:
-        out = {"time": torch.empty(B, dtype=torch.float64, device=dev),
-               "value": torch.empty(B, dtype=torch.float64, device=dev),
-               "segment": torch.empty(B, dtype=torch.int32, device=dev)}
+        out = _extremum_out(B, dev)
     check(lib().mtg_max_magnitude(N, D, S, B, _ptr(coeffs), _ptr(times), derivative,
                                   _ptr(out["time"]), _ptr(out["value"]), _ptr(out["segment"]),
                                   _stream(dev)), "mtg_max_magnitude")

@@ -727,15 +727,6 @@ __global__ void coll_opt_final_kernel(int64_t B, int nv, CollWs w, double* __res
 
 unsigned grid1(int64_t n) { return static_cast<unsigned>(n); }
 
-template <typename K>
-hipError_t prepare(K kernel, size_t bytes) {
-  if (bytes > 65536)
-    return hipFuncSetAttribute(reinterpret_cast<const void*>(kernel),
-                               hipFuncAttributeMaxDynamicSharedMemorySize,
-                               static_cast<int>(bytes));
-  return hipSuccess;
-}
-
 // One objective evaluation of the batch at xsrc (B x nv) up to the combine.
 template <int N>
 hipError_t evaluate_n(const PlanDev& pl, const CollDims& cd, int64_t B, const double* df,
@@ -743,11 +734,9 @@ hipError_t evaluate_n(const PlanDev& pl, const CollDims& cd, int64_t B, const do
                       int nz, const uint16_t* field, const mtg_coll_params& p, const CollWs& w,
                       hipStream_t st) {
   const size_t lds_prep = free_lds(N, pl.S, pl.D, pl.np, false).bytes;
-  hipError_t e = prepare(coll_prep_kernel<N>, lds_prep);
+  hipError_t e = launch(coll_prep_kernel<N>, B, kWave, lds_prep, st, pl, cd, df, times, xsrc,
+                        p.increment_time, w);
   if (e != hipSuccess) return e;
-  hipLaunchKernelGGL(coll_prep_kernel<N>, dim3(grid1(B)), dim3(kWave), lds_prep, st, pl, cd, df,
-                     times, xsrc, p.increment_time, w);
-  if ((e = hipGetLastError()) != hipSuccess) return e;
   const size_t lds_walk = collision_lds_bytes(N, pl.S);
   // With the near field one thread walks alone: one wave per walk.
   hipLaunchKernelGGL(coll_walk_kernel<N>, dim3(grid1(B * cd.P)),
@@ -775,17 +764,16 @@ hipError_t evaluate_n(const PlanDev& pl, const CollDims& cd, int64_t B, const do
   return hipSuccess;
 }
 
-}  // namespace
+hipError_t evaluate(const PlanDev& pl, const CollDims& cd, int64_t B, const double* df,
+                    const double* xsrc, const double* times, const float* occ, int nx, int ny,
+                    int nz, const uint16_t* field, const mtg_coll_params& p, const CollWs& w,
+                    hipStream_t st) {
+  return with_order(pl.N, [&](auto n) {
+    return evaluate_n<n()>(pl, cd, B, df, xsrc, times, occ, nx, ny, nz, field, p, w, st);
+  });
+}
 
-#define MTG_COLL_DISPATCH(FN, ...)        \
-  switch (pl.N) {                         \
-    case 4: e = FN<4>(__VA_ARGS__); break;   \
-    case 6: e = FN<6>(__VA_ARGS__); break;   \
-    case 8: e = FN<8>(__VA_ARGS__); break;   \
-    case 10: e = FN<10>(__VA_ARGS__); break; \
-    case 12: e = FN<12>(__VA_ARGS__); break; \
-    default: e = hipErrorInvalidValue;    \
-  }
+}  // namespace
 
 size_t coll_workspace_bytes(const PlanDev& pl, int64_t B, int mode, const mtg_coll_params& p,
                             bool optimiser) {
@@ -808,9 +796,8 @@ int coll_cost(const PlanDev& pl, int64_t B, int mode, const double* df, const do
   if (coll_workspace_bytes(pl, B, mode, p, false) > workspace_bytes) return MTG_ERR_INVALID_ARG;
   CollWs w;
   carve(workspace, cd, pl.N, B, p.n_soft, false, &w);
-  hipError_t e;
-  MTG_COLL_DISPATCH(evaluate_n, pl, cd, B, df, x, times, occ, nx, ny, nz, field, p, w, st)
-  if (e != hipSuccess) return MTG_ERR_HIP;
+  if (evaluate(pl, cd, B, df, x, times, occ, nx, ny, nz, field, p, w, st) != hipSuccess)
+    return MTG_ERR_HIP;
   const CombineOut o{raise_ref, cost, grad, terms, collision, status, nullptr};
   hipLaunchKernelGGL(coll_combine_kernel<false>, dim3(grid1(B)), dim3(kWave), 0, st, cd, p, 0,
                      Bounds{nullptr, nullptr}, w, o);
@@ -834,9 +821,8 @@ int coll_optimize(const PlanDev& pl, int64_t B, int mode, const double* df, doub
   CombineOut hist{};
   hist.x_history = x_history;
   for (int round = 0; round < max_evals; ++round) {
-    hipError_t e;
-    MTG_COLL_DISPATCH(evaluate_n, pl, cd, B, df, w.xt, times, occ, nx, ny, nz, field, p, w, st)
-    if (e != hipSuccess) return MTG_ERR_HIP;
+    if (evaluate(pl, cd, B, df, w.xt, times, occ, nx, ny, nz, field, p, w, st) != hipSuccess)
+      return MTG_ERR_HIP;
     hipLaunchKernelGGL(coll_combine_kernel<true>, dim3(grid1(B)), dim3(kWave), 0, st, cd, p,
                        max_evals, bd, w, hist);
     if (hipGetLastError() != hipSuccess) return MTG_ERR_HIP;

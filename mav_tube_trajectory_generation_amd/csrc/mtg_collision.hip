@@ -148,20 +148,11 @@ hipError_t launch_collision_cost(const PlanDev& pl, int64_t B, const double* coe
                                  const mtg_collision_params& p, double* cost, int32_t* coll,
                                  double* grad_coeffs, double* grad_free, hipStream_t st) {
   const size_t lds = collision_lds_bytes(pl.N, pl.S);
-#define CALL(n)                                                                              \
-  hipLaunchKernelGGL(collision_cost_kernel<n>, dim3(static_cast<unsigned>(B)), dim3(kCollBlock), \
-                     lds, st, pl.S, pl.np, pl.tab, pl.free_map, coeffs, times, occ, nx, ny, nz, \
-                     p, cost, coll, grad_coeffs, grad_free)
-  switch (pl.N) {
-    case 4: CALL(4); break;
-    case 6: CALL(6); break;
-    case 8: CALL(8); break;
-    case 10: CALL(10); break;
-    case 12: CALL(12); break;
-    default: return hipErrorInvalidValue;
-  }
-#undef CALL
-  return hipGetLastError();
+  return with_order(pl.N, [&](auto n) {
+    return launch(collision_cost_kernel<n()>, B, kCollBlock, lds, st, pl.S, pl.np, pl.tab,
+                  pl.free_map, coeffs, times, occ, nx, ny, nz, p, cost, coll, grad_coeffs,
+                  grad_free);
+  });
 }
 
 }  // namespace mtg

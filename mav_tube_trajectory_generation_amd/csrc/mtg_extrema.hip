@@ -113,9 +113,7 @@ __global__ __launch_bounds__(kExtBlock) void max_magnitude_kernel(
       for (int cidx = 0; cidx < kMaxSoftConstraints; ++cidx) {  // compile-time index
         if (cidx >= soft.lim.n) break;
         const double m = cidx == value_offset ? vmax : max_value[b * value_stride + cidx];
-        const double abs_violation = m - soft.lim.value[cidx];
-        const double relative_violation = abs_violation / soft.lim.value[cidx];
-        total += fmin(soft.maximum_cost, exp(relative_violation * soft.weight));
+        total += soft_penalty(m, soft.lim.value[cidx], soft.weight, soft.maximum_cost);
       }
       soft.cost[b] = total;
     }
@@ -148,30 +146,11 @@ static hipError_t launch_max_n(int K, int D, int S, int64_t B, int parts, int lo
   const int tpb = kExtBlock / (S * parts);
   const dim3 grid(static_cast<unsigned>((B + tpb - 1) / tpb));
   const size_t lds = sizeof(double) * static_cast<size_t>(tpb) * S * (D * N + 1);
-#define CALL(k)                                                                                \
-  if (lds > 65536) {                                                                           \
-    const hipError_t e = hipFuncSetAttribute(                                                  \
-        reinterpret_cast<const void*>(max_magnitude_kernel<N, k, kMin>),                       \
-        hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(lds));                     \
-    if (e != hipSuccess) return e;                                                             \
-  }                                                                                            \
-  hipLaunchKernelGGL((max_magnitude_kernel<N, k, kMin>), grid, dim3(kExtBlock), lds, st, D, S,    \
-                     B, parts, log2parts, coeffs, times, tmax, vmax, smax, stride, offset, soft,  \
-                     mino)
-  switch (K) {
-    case 0: CALL(0); break;
-    case 1: CALL(1); break;
-    case 2: CALL(2); break;
-    case 3:
-      if constexpr (N >= 5) { CALL(3); break; }
-      return hipErrorInvalidValue;
-    case 4:
-      if constexpr (N >= 6) { CALL(4); break; }
-      return hipErrorInvalidValue;
-    default: return hipErrorInvalidValue;
-  }
-#undef CALL
-  return hipGetLastError();
+  return with_derivative<N>(K, [&](auto k) {
+    return launch(max_magnitude_kernel<N, decltype(k)::value, kMin>, grid, kExtBlock, lds, st, D,
+                  S, B, parts, log2parts, coeffs, times, tmax, vmax, smax, stride, offset, soft,
+                  mino);
+  });
 }
 
 hipError_t launch_max_magnitude(int N, int D, int S, int64_t B, int derivative,
@@ -188,22 +167,14 @@ hipError_t launch_max_magnitude(int N, int D, int S, int64_t B, int derivative,
     --log2parts;
   }
   const MinOut none{};
-#define CALL(n)                                                                               \
-  (mino ? launch_max_n<n, true>(derivative, D, S, B, parts, log2parts, coeffs, times,          \
-                                max_time, max_value, max_segment, value_stride, value_offset, \
-                                soft, *mino, st)                                              \
-        : launch_max_n<n, false>(derivative, D, S, B, parts, log2parts, coeffs, times,         \
-                                 max_time, max_value, max_segment, value_stride, value_offset, \
-                                 soft, none, st))
-  switch (N) {
-    case 4: return CALL(4);
-    case 6: return CALL(6);
-    case 8: return CALL(8);
-    case 10: return CALL(10);
-    case 12: return CALL(12);
-    default: return hipErrorInvalidValue;
-  }
-#undef CALL
+  return with_order(N, [&](auto n) {
+    return mino ? launch_max_n<n(), true>(derivative, D, S, B, parts, log2parts, coeffs, times,
+                                          max_time, max_value, max_segment, value_stride,
+                                          value_offset, soft, *mino, st)
+                : launch_max_n<n(), false>(derivative, D, S, B, parts, log2parts, coeffs, times,
+                                           max_time, max_value, max_segment, value_stride,
+                                           value_offset, soft, none, st);
+  });
 }
 
 // ---------------------------------------------------------------------------
@@ -235,23 +206,10 @@ static hipError_t launch_cand_n(int K, int D, int64_t n_seg, const double* coeff
                                 const double* times, int cap, double* ct, double* cv,
                                 int32_t* nc, hipStream_t st) {
   const dim3 grid(static_cast<unsigned>((n_seg + kExtBlock - 1) / kExtBlock));
-#define CALL(k)                                                                           \
-  hipLaunchKernelGGL((magnitude_candidates_kernel<N, k>), grid, dim3(kExtBlock), 0, st, D, \
-                     n_seg, coeffs, times, cap, ct, cv, nc)
-  switch (K) {
-    case 0: CALL(0); break;
-    case 1: CALL(1); break;
-    case 2: CALL(2); break;
-    case 3:
-      if constexpr (N >= 5) { CALL(3); break; }
-      return hipErrorInvalidValue;
-    case 4:
-      if constexpr (N >= 6) { CALL(4); break; }
-      return hipErrorInvalidValue;
-    default: return hipErrorInvalidValue;
-  }
-#undef CALL
-  return hipGetLastError();
+  return with_derivative<N>(K, [&](auto k) {
+    return launch(magnitude_candidates_kernel<N, decltype(k)::value>, grid, kExtBlock, 0, st, D,
+                  n_seg, coeffs, times, cap, ct, cv, nc);
+  });
 }
 
 hipError_t launch_magnitude_candidates(int N, int D, int64_t n_seg, int derivative,
@@ -261,17 +219,10 @@ hipError_t launch_magnitude_candidates(int N, int D, int64_t n_seg, int derivati
   if (derivative < 0 || derivative > kMaxExtremaDerivative || N - derivative - 1 <= 0)
     return hipErrorInvalidValue;
   if (n_seg == 0) return hipSuccess;
-#define CALL(n) launch_cand_n<n>(derivative, D, n_seg, coeffs, times, cap, cand_time, \
-                                 cand_value, n_cand, st)
-  switch (N) {
-    case 4: return CALL(4);
-    case 6: return CALL(6);
-    case 8: return CALL(8);
-    case 10: return CALL(10);
-    case 12: return CALL(12);
-    default: return hipErrorInvalidValue;
-  }
-#undef CALL
+  return with_order(N, [&](auto n) {
+    return launch_cand_n<n()>(derivative, D, n_seg, coeffs, times, cap, cand_time, cand_value,
+                              n_cand, st);
+  });
 }
 
 // ---------------------------------------------------------------------------
@@ -304,7 +255,7 @@ __global__ __launch_bounds__(kSoftBlockMax) void soft_cost_kernel(int D, int S, 
   const int cidx = tid / group, r = tid - cidx * group;
   const bool group_on = cidx < spec.n;  // wave-uniform: groups are whole waves
   const bool active = group_on && r < S * parts;
-  double best_v = -1.0, best_t = 0.0, mv = 0.0, mt = 0.0;
+  double best_v = -1.0, best_t = 0.0;
   if (group_on) {
     const int s = active ? r >> log2parts : 0, part = r & (parts - 1);
     const double* c = c_s + s * D * N;
@@ -313,30 +264,9 @@ __global__ __launch_bounds__(kSoftBlockMax) void soft_cost_kernel(int D, int S, 
 #pragma unroll
     for (int q = 0; q < kMaxSoftConstraints; ++q)  // compile-time indices
       if (q == cidx) K = spec.derivative[q];
-    // Every lane of a wave searches the same trajectory and derivative, so
-    // the wave's largest |p^(K)|^2 at the parts' right ends bounds the
-    // maximum from below for the pruning (idle lanes give 0; all lanes of
-    // the wave take part in the exchange).
-#define MTG_SOFT_SEARCH(k)                                                                     \
-  {                                                                                            \
-    double lb = active ? ext_mag2<N, k>(c, D, ldexp(T * (part + 1), -log2parts)) : 0.0;       \
-    for (int off = 32; off > 0; off >>= 1) lb = fmax(lb, __shfl_xor(lb, off, 64));             \
-    if (active)                                                                                \
-      ext_segment_search<N, k>(c, D, T, part, parts, log2parts, best_v, best_t, mv, mt, lb);   \
-  }
-    switch (K) {
-      case 0: MTG_SOFT_SEARCH(0) break;
-      case 1: MTG_SOFT_SEARCH(1) break;
-      case 2: MTG_SOFT_SEARCH(2) break;
-      case 3:
-        if constexpr (N >= 5) MTG_SOFT_SEARCH(3)
-        break;
-      case 4:
-        if constexpr (N >= 6) MTG_SOFT_SEARCH(4)
-        break;
-      default: break;
-    }
-#undef MTG_SOFT_SEARCH
+    // Every lane of a wave searches the same trajectory and derivative:
+    // the wave-wide pruning bound holds (all lanes take part).
+    ext_search_wave_bound<N>(K, c, D, T, part, parts, log2parts, active, best_v, best_t);
   }
   val_s[tid] = best_v;
   __syncthreads();
@@ -357,8 +287,7 @@ __global__ __launch_bounds__(kSoftBlockMax) void soft_cost_kernel(int D, int S, 
       if (q >= spec.n) break;
       const double m = val_s[q * group];
       if (maxima) maxima[b * spec.n + q] = m;
-      const double relative_violation = (m - spec.limit[q]) / spec.limit[q];
-      total += fmin(spec.maximum_cost, exp(relative_violation * spec.weight));
+      total += soft_penalty(m, spec.limit[q], spec.weight, spec.maximum_cost);
     }
     cost[b] = total;
   }
@@ -378,28 +307,10 @@ hipError_t launch_soft_cost(int N, int D, int S, int64_t B, const double* coeffs
   const int threads = spec.n * group;
   if (threads > kSoftBlockMax) return hipErrorNotSupported;  // caller: one launch per constraint
   const size_t lds = sizeof(double) * (static_cast<size_t>(S) * D * N + S + threads);
-  const dim3 grid(static_cast<unsigned>(B));
-#define CALL(n)                                                                                 \
-  {                                                                                             \
-    if (lds > 65536) {                                                                          \
-      const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(soft_cost_kernel<n>), \
-                                               hipFuncAttributeMaxDynamicSharedMemorySize,      \
-                                               static_cast<int>(lds));                          \
-      if (e != hipSuccess) return e;                                                            \
-    }                                                                                           \
-    hipLaunchKernelGGL(soft_cost_kernel<n>, grid, dim3(threads), lds, st, D, S, parts, log2parts, \
-                       group, coeffs, times, spec, maxima, cost);                               \
-    return hipGetLastError();                                                                   \
-  }
-  switch (N) {
-    case 4: CALL(4)
-    case 6: CALL(6)
-    case 8: CALL(8)
-    case 10: CALL(10)
-    case 12: CALL(12)
-    default: return hipErrorInvalidValue;
-  }
-#undef CALL
+  return with_order(N, [&](auto n) {
+    return launch(soft_cost_kernel<n()>, B, threads, lds, st, D, S, parts, log2parts, group,
+                  coeffs, times, spec, maxima, cost);
+  });
 }
 
 // Soft-constraint cost of B problems by whichever launch shape fits: all

@@ -485,22 +485,62 @@ __device__ __attribute__((always_inline)) inline double ext_trajectory_max_wave(
   return sqrt(best);
 }
 
-// Runtime-derivative dispatch (POSITION..SNAP, nonlinear_impl:2697-2724).
+// Runtime-derivative dispatch (POSITION..SNAP, nonlinear_impl:2697-2724):
+// f(std::integral_constant<int, k>) for k = K where an order-N polynomial
+// has a derivative k + 1 to search, `otherwise` for any other K.  K must be
+// wave-uniform where f exchanges values across the wave.
+template <int N, typename R, typename F>
+__device__ __attribute__((always_inline)) inline R ext_with_derivative(int K, R otherwise, F f) {
+  switch (K) {
+    case 0: return f(std::integral_constant<int, 0>{});
+    case 1: return f(std::integral_constant<int, 1>{});
+    case 2: return f(std::integral_constant<int, 2>{});
+    case 3:
+      if constexpr (N >= 5) return f(std::integral_constant<int, 3>{});
+      return otherwise;
+    case 4:
+      if constexpr (N >= 6) return f(std::integral_constant<int, 4>{});
+      return otherwise;
+    default: return otherwise;
+  }
+}
+
 template <int N>
 __device__ __attribute__((always_inline)) inline double ext_trajectory_max_wave_k(int K, const double* coeffs,
                                                    const double* times, int S, int D, int lane) {
-  switch (K) {
-    case 0: return ext_trajectory_max_wave<N, 0>(coeffs, times, S, D, lane);
-    case 1: return ext_trajectory_max_wave<N, 1>(coeffs, times, S, D, lane);
-    case 2: return ext_trajectory_max_wave<N, 2>(coeffs, times, S, D, lane);
-    case 3:
-      if constexpr (N >= 5) return ext_trajectory_max_wave<N, 3>(coeffs, times, S, D, lane);
-      return 0.0;
-    case 4:
-      if constexpr (N >= 6) return ext_trajectory_max_wave<N, 4>(coeffs, times, S, D, lane);
-      return 0.0;
-    default: return 0.0;
-  }
+  return ext_with_derivative<N>(K, 0.0, [&](auto k) {
+    return ext_trajectory_max_wave<N, decltype(k)::value>(coeffs, times, S, D, lane);
+  });
+}
+
+// One lane's search of its part of a segment under a wave-wide pruning bound
+// (every lane of the wave calls, with one trajectory and a wave-uniform K):
+// the wave's largest |p^(K)|^2 at the parts' right ends, a value the
+// trajectory attains, bounds its maximum from below.  Idle lanes give 0 and
+// take part in the exchange only; active lanes then run ext_segment_search
+// into best_v / best_t.
+template <int N>
+__device__ __attribute__((always_inline)) inline void ext_search_wave_bound(
+    int K, const double* c, int D, double T, int part, int parts, int log2parts, bool active,
+    double& best_v, double& best_t) {
+  ext_with_derivative<N>(K, false, [&](auto k) {
+    constexpr int kK = decltype(k)::value;
+    double mv = 0.0, mt = 0.0;
+    double lb = active ? ext_mag2<N, kK>(c, D, ldexp(T * (part + 1), -log2parts)) : 0.0;
+    for (int off = 32; off > 0; off >>= 1) lb = fmax(lb, __shfl_xor(lb, off, 64));
+    if (active)
+      ext_segment_search<N, kK>(c, D, T, part, parts, log2parts, best_v, best_t, mv, mt, lb);
+    return true;
+  });
+}
+
+// One soft constraint's term of evaluateMaximumMagnitudeAsSoftConstraint
+// (nonlinear_impl:2747-2763) for the maximum m of a limited derivative.
+__device__ inline double soft_penalty(double m, double limit, double weight,
+                                      double maximum_cost) {
+  const double abs_violation = m - limit;
+  const double relative_violation = abs_violation / limit;
+  return fmin(maximum_cost, exp(relative_violation * weight));
 }
 
 // ---------------------------------------------------------------------------

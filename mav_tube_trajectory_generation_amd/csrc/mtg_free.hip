@@ -539,39 +539,36 @@ hipError_t time_free_sbplx_n(const PlanDev& pl, int64_t B, const double* df, dou
   });
 }
 
-#define MTG_FREE_DISPATCH(FN, ...)        \
-  switch (pl.N) {                         \
-    case 4: return FN<4>(__VA_ARGS__);    \
-    case 6: return FN<6>(__VA_ARGS__);    \
-    case 8: return FN<8>(__VA_ARGS__);    \
-    case 10: return FN<10>(__VA_ARGS__);  \
-    case 12: return FN<12>(__VA_ARGS__);  \
-    default: return hipErrorInvalidValue; \
-  }
-
 hipError_t launch_free_cost(const PlanDev& pl, int64_t B, const double* df, const double* dp,
                             const double* times, const mtg_time_params& p, int mode,
                             double* cost, double* grad, int32_t* status, hipStream_t st) {
-  MTG_FREE_DISPATCH(free_cost_n, pl, B, df, dp, times, p, mode, cost, grad, status, st)
+  return with_order(pl.N, [&](auto n) {
+    return free_cost_n<n()>(pl, B, df, dp, times, p, mode, cost, grad, status, st);
+  });
 }
 
 hipError_t launch_time_free_optimize(const PlanDev& pl, int64_t B, const double* df, double* dp,
                                      double* times, const mtg_time_params& p, int max_evals,
                                      double* cost, int32_t* evals, int32_t* result,
                                      int32_t* status, hipStream_t st) {
-  if (p.optimizer == 1) {
-    MTG_FREE_DISPATCH(time_free_sbplx_n, pl, B, df, dp, times, p, max_evals, cost, evals, result,
-                      status, st)
-  }
-  MTG_FREE_DISPATCH(time_free_opt_n, pl, B, df, dp, times, p, max_evals, cost, evals, status, st)
+  if (p.optimizer == 1)
+    return with_order(pl.N, [&](auto n) {
+      return time_free_sbplx_n<n()>(pl, B, df, dp, times, p, max_evals, cost, evals, result,
+                                    status, st);
+    });
+  return with_order(pl.N, [&](auto n) {
+    return time_free_opt_n<n()>(pl, B, df, dp, times, p, max_evals, cost, evals, status, st);
+  });
 }
 
 hipError_t launch_free_optimize(const PlanDev& pl, int64_t B, const double* df, double* dp,
                                 const double* times, const double* lower, const double* upper,
                                 const mtg_time_params& p, int max_evals, double* cost,
                                 int32_t* evals, int32_t* status, hipStream_t st) {
-  MTG_FREE_DISPATCH(free_opt_n, pl, B, df, dp, times, lower, upper, p, max_evals, cost, evals,
-                    status, st)
+  return with_order(pl.N, [&](auto n) {
+    return free_opt_n<n()>(pl, B, df, dp, times, lower, upper, p, max_evals, cost, evals, status,
+                           st);
+  });
 }
 
 }  // namespace mtg

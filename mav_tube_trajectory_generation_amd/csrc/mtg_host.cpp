@@ -476,13 +476,35 @@ int mtg_sample_trajectories(int N, int D, int S, int64_t B, const double* coeffs
                                      static_cast<hipStream_t>(stream)));
 }
 
+// A derivative whose magnitude extrema the kernels search: POSITION..SNAP
+// with a derivative of its own left in an order-N polynomial.
+static bool valid_extrema_derivative(int N, int derivative) {
+  return derivative >= 0 && derivative <= mtg::kMaxExtremaDerivative && N - derivative - 1 > 0;
+}
+
+// The soft constraints of an evaluation into `spec`; false where one is
+// invalid (addMaximumMagnitudeConstraint: CHECK_GE(derivative, 0),
+// CHECK_GE(value, 0)).  1 <= n_constraints <= kMaxSoftConstraints.
+static bool fill_soft_spec(int N, int n_constraints, const int* derivatives, const double* limits,
+                           double weight, double maximum_cost, mtg::SoftSpec* spec) {
+  spec->n = n_constraints;
+  spec->weight = weight;
+  spec->maximum_cost = maximum_cost;
+  for (int c = 0; c < n_constraints; ++c) {
+    if (!valid_extrema_derivative(N, derivatives[c]) || !(limits[c] >= 0.0)) return false;
+    spec->derivative[c] = derivatives[c];
+    spec->limit[c] = limits[c];
+  }
+  return true;
+}
+
 int mtg_magnitude_candidates(int N, int D, int S, int64_t B, const double* coeffs,
                              const double* times, int derivative, int max_candidates,
                              double* cand_time, double* cand_value, int32_t* n_candidates,
                              void* stream) {
   clear_stale_error();
-  if (!valid_N(N) || D < 1 || D > mtg::kMaxD || S < 1 || B < 0 || derivative < 0 ||
-      derivative > mtg::kMaxExtremaDerivative || N - derivative - 1 <= 0 || max_candidates < 2)
+  if (!valid_N(N) || D < 1 || D > mtg::kMaxD || S < 1 || B < 0 ||
+      !valid_extrema_derivative(N, derivative) || max_candidates < 2)
     return MTG_ERR_INVALID_ARG;
   if (B == 0) return MTG_OK;
   if (!coeffs || !times || !cand_time || !cand_value || !n_candidates) return MTG_ERR_INVALID_ARG;
@@ -496,8 +518,8 @@ int mtg_max_magnitude(int N, int D, int S, int64_t B, const double* coeffs,
                       const double* times, int derivative, double* max_time,
                       double* max_value, int32_t* max_segment, void* stream) {
   clear_stale_error();
-  if (!valid_N(N) || D < 1 || D > mtg::kMaxD || S < 1 || S > 256 || B < 0 || derivative < 0 ||
-      derivative > mtg::kMaxExtremaDerivative || N - derivative - 1 <= 0)
+  if (!valid_N(N) || D < 1 || D > mtg::kMaxD || S < 1 || S > 256 || B < 0 ||
+      !valid_extrema_derivative(N, derivative))
     return MTG_ERR_INVALID_ARG;
   if (B == 0) return MTG_OK;
   if (!coeffs || !times) return MTG_ERR_INVALID_ARG;
@@ -537,8 +559,8 @@ int mtg_min_max_magnitude(int N, int D, int S, int64_t B, const double* coeffs,
                           double* min_value, int32_t* min_segment, double* max_time,
                           double* max_value, int32_t* max_segment, void* stream) {
   clear_stale_error();
-  if (!valid_N(N) || D < 1 || D > mtg::kMaxD || S < 1 || S > 256 || B < 0 || derivative < 0 ||
-      derivative > mtg::kMaxExtremaDerivative || N - derivative - 1 <= 0)
+  if (!valid_N(N) || D < 1 || D > mtg::kMaxD || S < 1 || S > 256 || B < 0 ||
+      !valid_extrema_derivative(N, derivative))
     return MTG_ERR_INVALID_ARG;
   if (B == 0) return MTG_OK;
   if (!coeffs || !times) return MTG_ERR_INVALID_ARG;
@@ -559,17 +581,8 @@ int mtg_soft_constraint_cost(int N, int D, int S, int64_t B, const double* coeff
       !limits)
     return MTG_ERR_INVALID_ARG;
   mtg::SoftSpec spec{};
-  spec.n = n_constraints;
-  spec.weight = weight;
-  spec.maximum_cost = maximum_cost;
-  for (int c = 0; c < n_constraints; ++c) {
-    // addMaximumMagnitudeConstraint: CHECK_GE(derivative, 0), CHECK_GE(value, 0)
-    if (derivatives[c] < 0 || derivatives[c] > mtg::kMaxExtremaDerivative ||
-        N - derivatives[c] - 1 <= 0 || !(limits[c] >= 0.0))
-      return MTG_ERR_INVALID_ARG;
-    spec.derivative[c] = derivatives[c];
-    spec.limit[c] = limits[c];
-  }
+  if (!fill_soft_spec(N, n_constraints, derivatives, limits, weight, maximum_cost, &spec))
+    return MTG_ERR_INVALID_ARG;
   if (B == 0) return MTG_OK;
   if (!coeffs || !times || !maxima || !cost) return MTG_ERR_INVALID_ARG;
   if (B > 0x7fffffff) return MTG_ERR_INVALID_ARG;
@@ -1022,10 +1035,6 @@ static int ragged_eval_sizes(int N, int D, int S_max, int64_t B) {
   return MTG_OK;
 }
 
-static bool valid_extrema_derivative(int N, int derivative) {
-  return derivative >= 0 && derivative <= mtg::kMaxExtremaDerivative && N - derivative - 1 > 0;
-}
-
 int mtg_ragged_max_magnitude(int N, int D, int S_max, int64_t B, const int32_t* seg_counts,
                              const double* coeffs, const double* times, int derivative,
                              double* max_time, double* max_value, int32_t* max_segment,
@@ -1059,16 +1068,8 @@ int mtg_ragged_soft_constraint_cost(int N, int D, int S_max, int64_t B, const in
       B > 0x7fffffff)
     return MTG_ERR_INVALID_ARG;
   mtg::SoftSpec spec{};
-  spec.n = n_constraints;
-  spec.weight = weight;
-  spec.maximum_cost = maximum_cost;
-  for (int c = 0; c < n_constraints; ++c) {
-    // addMaximumMagnitudeConstraint: CHECK_GE(derivative, 0), CHECK_GE(value, 0)
-    if (!valid_extrema_derivative(N, derivatives[c]) || !(limits[c] >= 0.0))
-      return MTG_ERR_INVALID_ARG;
-    spec.derivative[c] = derivatives[c];
-    spec.limit[c] = limits[c];
-  }
+  if (!fill_soft_spec(N, n_constraints, derivatives, limits, weight, maximum_cost, &spec))
+    return MTG_ERR_INVALID_ARG;
   if (mtg::ragged_extrema_lds_bytes(N, S_max, D) > static_cast<size_t>(mtg::kMaxLdsBytes))
     return MTG_ERR_UNSUPPORTED;
   if (B == 0) return MTG_OK;

@@ -1,6 +1,8 @@
 // mtg_internal.h — shared between the host ABI (mtg_host.cpp) and the kernel
-// launchers (mtg_kernels.hip, mtg_tube.hip), with the launch helpers the
-// launchers share.  Not part of the public ABI.
+// launchers (every mtg_*.hip), with the helpers the launchers share: launch /
+// prepare_lds (the one place the dynamic-LDS limit is raised), with_soft,
+// with_order (the one list of polynomial orders) and with_derivative.  Not
+// part of the public ABI.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stddef.h>
@@ -237,19 +239,41 @@ hipError_t prepare_lds(K kernel, size_t bytes) {
 }
 // prepare_lds, launch `grid` workgroups of `threads`, hipGetLastError.
 template <typename... P, typename... A>
-hipError_t launch(void (*kernel)(P...), int64_t grid, int threads, size_t lds_bytes,
+hipError_t launch(void (*kernel)(P...), dim3 grid, int threads, size_t lds_bytes,
                   hipStream_t st, A... args) {
   const hipError_t e = prepare_lds(kernel, lds_bytes);
   if (e != hipSuccess) return e;
-  hipLaunchKernelGGL(kernel, dim3(static_cast<unsigned>(grid)), dim3(threads), lds_bytes, st,
-                     args...);
+  hipLaunchKernelGGL(kernel, grid, dim3(threads), lds_bytes, st, args...);
   return hipGetLastError();
+}
+template <typename... P, typename... A>
+hipError_t launch(void (*kernel)(P...), int64_t grid, int threads, size_t lds_bytes,
+                  hipStream_t st, A... args) {
+  return launch(kernel, dim3(static_cast<unsigned>(grid)), threads, lds_bytes, st, args...);
 }
 // f(std::true_type) or f(std::false_type) by `soft`: the launchers of the
 // kernels templated on kSoft name K<..., decltype(soft)::value> once.
 template <typename F>
 hipError_t with_soft(bool soft, F f) {
   return soft ? f(std::true_type{}) : f(std::false_type{});
+}
+// f(std::integral_constant<int, n>) for the polynomial order n = N, the one
+// list of the orders the kernels are instantiated for; `invalid` (of f's
+// return type: hipError_t, or an MTG_* code) for any other N.
+template <typename F, typename R>
+R with_order(int N, F f, R invalid) {
+  switch (N) {
+    case 4: return f(std::integral_constant<int, 4>{});
+    case 6: return f(std::integral_constant<int, 6>{});
+    case 8: return f(std::integral_constant<int, 8>{});
+    case 10: return f(std::integral_constant<int, 10>{});
+    case 12: return f(std::integral_constant<int, 12>{});
+    default: return invalid;
+  }
+}
+template <typename F>
+hipError_t with_order(int N, F f) {
+  return with_order(N, f, hipErrorInvalidValue);
 }
 
 // Trajectory sampling (mtg_sample.hip).
@@ -261,6 +285,24 @@ hipError_t launch_sample(int N, int D, int S, int64_t B, const double* coeffs,
 
 // Magnitude extrema and soft constraints (mtg_extrema.hip).
 constexpr int kMaxExtremaDerivative = 4;  // POSITION..SNAP (nonlinear_impl:2697-2724)
+// f(std::integral_constant<int, k>) for the derivative k = K whose extrema
+// an order-N polynomial has kernels for (the guards of ext_with_derivative,
+// mtg_extrema_device.h); hipErrorInvalidValue otherwise.
+template <int N, typename F>
+hipError_t with_derivative(int K, F f) {
+  switch (K) {
+    case 0: return f(std::integral_constant<int, 0>{});
+    case 1: return f(std::integral_constant<int, 1>{});
+    case 2: return f(std::integral_constant<int, 2>{});
+    case 3:
+      if constexpr (N >= 5) return f(std::integral_constant<int, 3>{});
+      return hipErrorInvalidValue;
+    case 4:
+      if constexpr (N >= 6) return f(std::integral_constant<int, 4>{});
+      return hipErrorInvalidValue;
+    default: return hipErrorInvalidValue;
+  }
+}
 constexpr int kMaxSoftConstraints = 8;
 struct SoftLimits {
   int n;

@@ -329,16 +329,6 @@ static hipError_t launch_time_opt_n(const PlanDev& pl, int64_t B, const double* 
   });
 }
 
-#define MTG_DISPATCH_N(N_, CALL)     \
-  switch (N_) {                      \
-    case 4: return CALL(4);          \
-    case 6: return CALL(6);          \
-    case 8: return CALL(8);          \
-    case 10: return CALL(10);        \
-    case 12: return CALL(12);        \
-    default: return hipErrorInvalidValue; \
-  }
-
 int linear_kernel_for_batch(const PlanDev& pl, int64_t B) {
   if (pl.kernel != MTG_KERNEL_AUTO) return pl.kernel;
   if (!pl.std_pattern) return MTG_KERNEL_GENERIC;
@@ -391,16 +381,9 @@ hipError_t launch_linear_solve(const PlanDev& pl, int64_t B, const double* df,
     if (e != hipSuccess || !sel.out) return e;
     return launch_select_local(cost, B, sel.start, sel.rank, sel.out, st);
   }
-#define CALL(n) launch_linear_n<n>(pl, B, df, times, coeffs, cost, free_vals, status, st)
-  switch (pl.N) {
-    case 4: e = CALL(4); break;
-    case 6: e = CALL(6); break;
-    case 8: e = CALL(8); break;
-    case 10: e = CALL(10); break;
-    case 12: e = CALL(12); break;
-    default: return hipErrorInvalidValue;
-  }
-#undef CALL
+  e = with_order(pl.N, [&](auto n) {
+    return launch_linear_n<n()>(pl, B, df, times, coeffs, cost, free_vals, status, st);
+  });
   if (e != hipSuccess || !sel.out) return e;
   return launch_select_local(cost, B, sel.start, sel.rank, sel.out, st);
 }
@@ -409,9 +392,9 @@ hipError_t launch_coeffs_from_constraints(const PlanDev& pl, int64_t B, const do
                                           const double* dp, const double* times,
                                           double* coeffs, double* cost, int32_t* status,
                                           hipStream_t st) {
-#define CALL(n) launch_coeffs_n<n>(pl, B, df, dp, times, coeffs, cost, status, st)
-  MTG_DISPATCH_N(pl.N, CALL)
-#undef CALL
+  return with_order(pl.N, [&](auto n) {
+    return launch_coeffs_n<n()>(pl, B, df, dp, times, coeffs, cost, status, st);
+  });
 }
 
 hipError_t launch_time_cost(const PlanDev& pl, int64_t B, const double* df,
@@ -419,9 +402,9 @@ hipError_t launch_time_cost(const PlanDev& pl, int64_t B, const double* df,
                             double* cost, double* grad, int32_t* status,
                             hipStream_t st) {
   if (has_time_std(pl)) return launch_time_cost_std(pl, B, df, times, p, cost, grad, status, st);
-#define CALL(n) launch_time_cost_n<n>(pl, B, df, times, p, cost, grad, status, st)
-  MTG_DISPATCH_N(pl.N, CALL)
-#undef CALL
+  return with_order(pl.N, [&](auto n) {
+    return launch_time_cost_n<n()>(pl, B, df, times, p, cost, grad, status, st);
+  });
 }
 
 hipError_t launch_time_optimize(const PlanDev& pl, int64_t B, const double* df,
@@ -431,10 +414,10 @@ hipError_t launch_time_optimize(const PlanDev& pl, int64_t B, const double* df,
   if (has_time_std(pl))
     return launch_time_optimize_std(pl, B, df, times, p, max_evals, cost, evals, solves, result,
                                     status, st);
-#define CALL(n) \
-  launch_time_opt_n<n>(pl, B, df, times, p, max_evals, cost, evals, solves, result, status, st)
-  MTG_DISPATCH_N(pl.N, CALL)
-#undef CALL
+  return with_order(pl.N, [&](auto n) {
+    return launch_time_opt_n<n()>(pl, B, df, times, p, max_evals, cost, evals, solves, result,
+                                  status, st);
+  });
 }
 
 hipError_t launch_segment_matrices(int N, int r, int64_t n, const double* tab,

@@ -151,14 +151,10 @@ hipError_t launch_linear_solve_std(const PlanDev& pl, int64_t B, const double* d
                                              sel.rank, sel.prev_out, st);
     if (e != hipSuccess) return e;
   }
-  switch (pl.N) {
-    case 4: return launch_std_n<4>(pl.r, pl.D, pl.S, B, pl.tab, df, times, coeffs, cost, free_vals, status, st);
-    case 6: return launch_std_n<6>(pl.r, pl.D, pl.S, B, pl.tab, df, times, coeffs, cost, free_vals, status, st);
-    case 8: return launch_std_n<8>(pl.r, pl.D, pl.S, B, pl.tab, df, times, coeffs, cost, free_vals, status, st);
-    case 10: return launch_std_n<10>(pl.r, pl.D, pl.S, B, pl.tab, df, times, coeffs, cost, free_vals, status, st);
-    case 12: return launch_std_n<12>(pl.r, pl.D, pl.S, B, pl.tab, df, times, coeffs, cost, free_vals, status, st);
-    default: return hipErrorInvalidValue;
-  }
+  return with_order(pl.N, [&](auto n) {
+    return launch_std_n<n()>(pl.r, pl.D, pl.S, B, pl.tab, df, times, coeffs, cost, free_vals,
+                             status, st);
+  });
 }
 
 }  // namespace mtg

@@ -292,14 +292,10 @@ hipError_t launch_ragged_linear_solve(const RaggedDev& pl, int64_t B, const int3
                                       const double* df, const double* times, double* coeffs,
                                       double* cost, double* free_vals, int32_t* status,
                                       hipStream_t st) {
-  switch (pl.N) {
-    case 4: return ragged_linear_n<4>(pl, B, seg_counts, df, times, coeffs, cost, free_vals, status, st);
-    case 6: return ragged_linear_n<6>(pl, B, seg_counts, df, times, coeffs, cost, free_vals, status, st);
-    case 8: return ragged_linear_n<8>(pl, B, seg_counts, df, times, coeffs, cost, free_vals, status, st);
-    case 10: return ragged_linear_n<10>(pl, B, seg_counts, df, times, coeffs, cost, free_vals, status, st);
-    case 12: return ragged_linear_n<12>(pl, B, seg_counts, df, times, coeffs, cost, free_vals, status, st);
-    default: return hipErrorInvalidValue;
-  }
+  return with_order(pl.N, [&](auto n) {
+    return ragged_linear_n<n()>(pl, B, seg_counts, df, times, coeffs, cost, free_vals, status,
+                                st);
+  });
 }
 
 hipError_t launch_ragged_time_cost(const RaggedDev& pl, int64_t B, const int32_t* seg_counts,

@@ -106,8 +106,7 @@ __device__ __attribute__((always_inline)) double std_objective(SV& sv, const dou
       if (p.hard_constraints) {
         *viol = fmax(*viol, m - lim - p.hard_tolerance);
       } else {
-        const double relative_violation = (m - lim) / lim;
-        soft += fmin(p.soft_maximum_cost, exp(relative_violation * p.soft_weight));
+        soft += soft_penalty(m, lim, p.soft_weight, p.soft_maximum_cost);
       }
       MTG_TACC(451 + c, tt);  // diagnostic
     }

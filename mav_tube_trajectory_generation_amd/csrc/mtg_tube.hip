@@ -234,29 +234,17 @@ hipError_t solve_n(const TubeArgs& a, double tol, int max_iter, double* x, doubl
 }
 }  // namespace
 
-#define MTG_TUBE_DISPATCH(CALL)              \
-  switch (a.N) {                             \
-    case 4: return CALL(4);                  \
-    case 6: return CALL(6);                  \
-    case 8: return CALL(8);                  \
-    case 10: return CALL(10);                \
-    case 12: return CALL(12);                \
-    default: return hipErrorInvalidValue;    \
-  }
-
 hipError_t launch_tube_residuals(const TubeArgs& a, const double* x, double* resid,
                                  hipStream_t st) {
-#define CALL(n) residuals_n<n>(a, x, resid, st)
-  MTG_TUBE_DISPATCH(CALL)
-#undef CALL
+  return with_order(a.N, [&](auto n) { return residuals_n<n()>(a, x, resid, st); });
 }
 
 hipError_t launch_tube_solve(const TubeArgs& a, double tol, int max_iter, double* x,
                              double* coeffs, double* cost, int32_t* iters, int32_t* status,
                              hipStream_t st) {
-#define CALL(n) solve_n<n>(a, tol, max_iter, x, coeffs, cost, iters, status, st)
-  MTG_TUBE_DISPATCH(CALL)
-#undef CALL
+  return with_order(a.N, [&](auto n) {
+    return solve_n<n()>(a, tol, max_iter, x, coeffs, cost, iters, status, st);
+  });
 }
 
 }  // namespace mtg
