@@ -859,6 +859,61 @@ int64_t mtg_coll_field_bytes(int nx, int ny, int nz);
 int mtg_coll_field(const float* occupancy, int nx, int ny, int nz,
                    const mtg_collision_params* params, uint16_t* field, void* stream);
 
+/* ------------------------------------------------------------------------
+ * Collision walk over a ragged batch: mtg_collision_cost over the arrays a
+ * ragged solve writes, in one launch, with a gate and the hit location.
+ * Plan-free like the ragged evaluators above, whose layout it shares:
+ * seg_counts B (int32, device, read by the kernel only, so a captured launch
+ * may be replayed over other counts), coeffs B x S_max x 3 x N and times
+ * B x S_max of which only the first S_b segments of a row are read (the
+ * padding may be NaN).  D is 3.
+ *
+ * Per row b, cost, collision (0 / 1) and grad_coeffs are exactly what
+ * mtg_collision_cost gives for coeffs[b, :S_b], times[b, :S_b], the
+ * reference's partial gradient on a collision and cost 0 there included.
+ * grad_coeffs is B x S_max x 3 x N; segments >= S_b are written 0.0.
+ *
+ * near_field (nullable) is the mtg_coll_field of the same occupancy and
+ * box_side.  With it one 64-lane workgroup walks a row with one load per
+ * evaluated sample (a sample whose voxel lies outside the grid still scans
+ * its box); without it a 256-thread workgroup scans every evaluated sample's
+ * box.  The results are bit-identical.
+ *
+ * Hit location: the first colliding evaluated sample gives hit_segment[b]
+ * and hit_time[b], that sample's t within its segment (the walk's repeated
+ * addition of coll_check_time_increment from the segment's start); without
+ * a collision -1 and NaN.  A sample that collides because it is within one
+ * voxel of the bounds counts like any other.
+ *
+ * Gate: gate_out[b] = gate_in[b] where collision[b] == 0 and +inf elsewhere;
+ * a NaN gate_in passes through; gate_out may alias gate_in; gate_out without
+ * gate_in is invalid.  Chained after mtg_ragged_soft_constraint_cost's gate,
+ * mtg_select_local picks the cheapest feasible, collision-free row:
+ * solve -> feasible -> collision-free -> select -> sample with no host step.
+ *
+ * Every output is nullable.  With grad_coeffs NULL (the gate-only launch)
+ * the walk accumulates no gradient and the workgroup holds neither the
+ * gradient nor the walk's gradient rows in LDS.
+ *
+ * A row whose count is outside [1, S_max] touches nothing outside its own
+ * row: cost NaN, collision -1, hit_segment -1, hit_time NaN, its whole
+ * padded grad_coeffs row NaN, gate_out +inf.
+ *
+ * N in {4, 6, 8, 10, 12}; 1 <= S_max <= 64 (MTG_ERR_INVALID_ARG below 1,
+ * MTG_ERR_UNSUPPORTED above 64, both before any pointer is looked at);
+ * 0 <= B <= 0x7fffffff; params as mtg_collision_cost; with a near field
+ * box_side <= 31; the LDS for S_max is checked against mtg_collision_cost's
+ * 64 KiB (MTG_ERR_UNSUPPORTED).  B == 0 returns MTG_OK and launches nothing;
+ * NULL seg_counts, coeffs or times, or NULL occupancy with a non-empty grid,
+ * is MTG_ERR_INVALID_ARG. */
+int mtg_ragged_collision_cost(int N, int S_max, int64_t B, const int32_t* seg_counts,
+                              const double* coeffs, const double* times,
+                              const float* occupancy, int nx, int ny, int nz,
+                              const uint16_t* near_field, const mtg_collision_params* params,
+                              double* cost, int32_t* collision, int32_t* hit_segment,
+                              double* hit_time, double* grad_coeffs, const double* gate_in,
+                              double* gate_out, void* stream);
+
 int64_t mtg_coll_workspace_bytes(const mtg_plan* plan, int64_t B, int mode,
                                  const mtg_coll_params* params, int optimize);
 /* near_field: mtg_coll_field of the same occupancy and box_side, or NULL

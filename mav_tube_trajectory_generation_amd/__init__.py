@@ -12,7 +12,7 @@ from .batch import (Context, LinearPlan, RaggedLinearPlan, coll_field,  # noqa: 
                     generate_random_problems,
                     magnitude_candidates,
                     max_magnitude,
-                    min_max_magnitude, pack_ragged, ragged_max_magnitude,
+                    min_max_magnitude, pack_ragged, ragged_collision_cost, ragged_max_magnitude,
                     ragged_sample_trajectories, ragged_soft_constraint_cost,
                     sample_trajectories, segment_matrices,
                     soft_constraint_cost,
@@ -25,7 +25,7 @@ __all__ = ["Context", "LinearPlan", "RaggedLinearPlan", "pack_ragged", "MTGError
            "max_magnitude",
            "min_max_magnitude", "make_coll_params", "make_collision_params", "make_time_params",
            "COLL_DEFAULTS",
-           "ragged_max_magnitude", "ragged_sample_trajectories", "ragged_soft_constraint_cost",
+           "ragged_collision_cost", "ragged_max_magnitude", "ragged_sample_trajectories", "ragged_soft_constraint_cost",
            "sample_trajectories", "segment_matrices", "soft_constraint_cost",
            "tube_num_constraints", "tube_residuals", "tube_solve", "tube_time_cost",
            "tube_time_optimize", "tube_time_workspace_bytes", "lib", "LIB_PATH"]

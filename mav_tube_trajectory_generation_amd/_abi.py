@@ -228,6 +228,11 @@ SIGNATURES = {
                                                       ctypes.c_double, ctypes.c_double,
                                                       ctypes.c_double, ctypes.c_int, ctypes.c_int,
                                                       _vp, _vp, _vp, _vp]),
+    "mtg_ragged_collision_cost": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_int64,
+                                                 _vp, _vp, _vp, _vp, ctypes.c_int, ctypes.c_int,
+                                                 ctypes.c_int, _vp,
+                                                 ctypes.POINTER(CollisionParams), _vp, _vp, _vp,
+                                                 _vp, _vp, _vp, _vp, _vp]),
     "mtg_tube_num_constraints": (ctypes.c_int, [ctypes.c_int, ctypes.c_int]),
     "mtg_tube_residuals": (ctypes.c_int, [_vp, ctypes.c_int, ctypes.c_int, ctypes.c_int,
                                           ctypes.c_int64, _vp, _vp, _vp, _vp, _vp, _vp, _vp,

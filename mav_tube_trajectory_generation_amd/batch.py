@@ -734,6 +734,67 @@ def ragged_soft_constraint_cost(seg_counts, coeffs, times, derivatives, limits, 
     return out
 
 
+def ragged_collision_cost(seg_counts, coeffs, times, occupancy, params, near_field=None,
+                          grad=False, gate=None, out=None):
+    """LinearPlan.collision_cost over a ragged batch in one launch
+    (mtg_ragged_collision_cost), inputs as ragged_max_magnitude with D = 3;
+    occupancy float32 CUDA tensor [nz, ny, nx] (occupied iff >= 0), params
+    from make_collision_params, near_field from coll_field(occupancy, params)
+    (None: every evaluated sample's box is scanned; the results are the same
+    bit for bit).
+
+    Returns a dict of cost [B], collision [B] int32 (0 / 1), hit_segment [B]
+    int32 and hit_time [B]: the first colliding sample's segment and its t
+    within that segment (-1 and NaN on a free row); with grad also grad_coeffs
+    [B, S_max, 3, N] (0.0 past each row's count); with gate [B] (typically the
+    solve's cost, or ragged_soft_constraint_cost's gated) also gated [B]:
+    gate[b] on a collision-free row, +inf elsewhere (a NaN gate passes
+    through).  out["gated"] may be gate itself.  A row whose count is outside
+    [1, S_max] gets cost NaN, collision -1, hit_segment -1, hit_time NaN,
+    grad_coeffs NaN and gated +inf.  The counts stay on the device."""
+    import torch
+    B, S_max, D, N = _ragged_eval_inputs(seg_counts, coeffs, times)
+    if D != 3:
+        raise MTGError(f"coeffs has D = {D}; the collision walk needs D = 3")
+    if not (isinstance(occupancy, torch.Tensor) and occupancy.is_cuda and
+            occupancy.dtype == torch.float32 and occupancy.dim() == 3 and
+            occupancy.is_contiguous()):
+        raise MTGError("occupancy must be a contiguous float32 CUDA tensor [nz, ny, nx]")
+    _check_field(near_field, occupancy)
+    if gate is not None:
+        _require(gate, (B,), "gate")
+    nz, ny, nx = occupancy.shape
+    dev = times.device
+    out = dict(out) if out is not None else {}
+    for key in ("cost", "hit_time"):
+        if key not in out:
+            out[key] = torch.empty(B, dtype=torch.float64, device=dev)
+        _require(out[key], (B,), key)
+    for key in ("collision", "hit_segment"):
+        if key not in out:
+            out[key] = torch.empty(B, dtype=torch.int32, device=dev)
+        if not (isinstance(out[key], torch.Tensor) and out[key].is_cuda and
+                out[key].dtype == torch.int32 and tuple(out[key].shape) == (B,) and
+                out[key].is_contiguous()):
+            raise MTGError(f"{key} must be a contiguous int32 CUDA tensor of shape {(B,)}")
+    if grad:
+        if "grad_coeffs" not in out:
+            out["grad_coeffs"] = torch.empty((B, S_max, D, N), dtype=torch.float64, device=dev)
+        _require(out["grad_coeffs"], (B, S_max, D, N), "grad_coeffs")
+    if gate is not None:
+        if "gated" not in out:
+            out["gated"] = torch.empty(B, dtype=torch.float64, device=dev)
+        _require(out["gated"], (B,), "gated")
+    check(lib().mtg_ragged_collision_cost(
+        N, S_max, B, _ptr(seg_counts), _ptr(coeffs), _ptr(times), _ptr(occupancy), nx, ny, nz,
+        _ptr(near_field), ctypes.byref(params), _ptr(out["cost"]), _ptr(out["collision"]),
+        _ptr(out["hit_segment"]), _ptr(out["hit_time"]),
+        _ptr(out["grad_coeffs"] if grad else None), _ptr(gate),
+        _ptr(out["gated"] if gate is not None else None), _stream(dev)),
+        "mtg_ragged_collision_cost")
+    return out
+
+
 def ragged_sample_trajectories(seg_counts, coeffs, times, dt, t_start=0.0, t_end=-1.0,
                                max_derivative=0, n_max=None, with_times=True):
     """sample_trajectories over a ragged batch in one launch

@@ -175,14 +175,17 @@ __device__ inline void coll_wave_sync() {
 //      coefficient gradient adding sample after sample from the LDS rows.
 // Every floating-point sum runs in the reference's order, so a chunked walk
 // equals the sample-by-sample one bit for bit.
-template <int N>
+// With kHitLoc the first colliding evaluated sample's segment and time within
+// it are left in the spare control words scratch[4] and scratch[5] (written
+// only on a collision; mtg_ragged_coll.hip reads them after the walk).
+template <int N, bool kHitLoc = false>
 __device__ void collision_walk(int S, const double* c_s, const double* T_s, const float* occ,
                                int nx, int ny, int nz, const mtg_collision_params& p, bool grad,
                                double* g_s, double* scratch, double* J_out, bool* hit_out,
                                const uint16_t* field = nullptr) {
   constexpr int D = 3, RW = N + 6;
   static_assert(D * N <= kWave, "one lane per gradient coefficient");
-  double* ctl = scratch;                           // [0] chunk, [1] boxes, [2] J, [3] hit
+  double* ctl = scratch;  // [0] chunk, [1] boxes, [2] J, [3] hit, [4] hit segment, [5] hit t
   int* evl = reinterpret_cast<int*>(scratch + 8);  // kWave x {vx, vy, vz, lane}
   double* red = scratch + 8 + 2 * kWave;
   double* rows = red + 7 * (kCollBlock / kWave);   // kWave x RW
@@ -340,6 +343,12 @@ __device__ void collision_walk(int S, const double* c_s, const double* T_s, cons
       }
       if (cm) {
         hit = true;
+        if constexpr (kHitLoc) {
+          if (lane == __builtin_ctzll(cm)) {
+            ctl[4] = seg;
+            ctl[5] = tj;
+          }
+        }
       } else {
         for (int d = 0; d < D; ++d) prev[d] = coll_readlane(pos[d], n_in - 1);
         // A segment ends at its first t >= T (a full chunk continues; one

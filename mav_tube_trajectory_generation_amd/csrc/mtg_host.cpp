@@ -1104,6 +1104,33 @@ int mtg_ragged_sample_trajectories(int N, int D, int S_max, int64_t B, const int
                                             static_cast<hipStream_t>(stream)));
 }
 
+int mtg_ragged_collision_cost(int N, int S_max, int64_t B, const int32_t* seg_counts,
+                              const double* coeffs, const double* times,
+                              const float* occupancy, int nx, int ny, int nz,
+                              const uint16_t* near_field, const mtg_collision_params* params,
+                              double* cost, int32_t* collision, int32_t* hit_segment,
+                              double* hit_time, double* grad_coeffs, const double* gate_in,
+                              double* gate_out, void* stream) {
+  clear_stale_error();
+  const int rc = ragged_eval_sizes(N, 3, S_max, B);
+  if (rc) return rc;
+  if (B > 0x7fffffff || !params || !valid_collision_params(*params, nx, ny, nz))
+    return MTG_ERR_INVALID_ARG;
+  if (near_field && !mtg::coll_field_supported(params->box_side)) return MTG_ERR_INVALID_ARG;
+  // the limit of mtg_collision_cost
+  if (mtg::ragged_collision_lds_bytes(N, S_max, grad_coeffs != nullptr) > 65536)
+    return MTG_ERR_UNSUPPORTED;
+  if (B == 0) return MTG_OK;
+  if (!seg_counts || !coeffs || !times || (gate_out && !gate_in) ||
+      (!occupancy && static_cast<int64_t>(nx) * ny * nz > 0))
+    return MTG_ERR_INVALID_ARG;
+  const mtg::RaggedCollOut out{cost, collision, hit_segment, hit_time, grad_coeffs, gate_in,
+                               gate_out};
+  return from_hip(mtg::launch_ragged_collision(N, S_max, B, seg_counts, coeffs, times, occupancy,
+                                               nx, ny, nz, near_field, *params, out,
+                                               static_cast<hipStream_t>(stream)));
+}
+
 int mtg_tube_num_constraints(int N, int S) {
   if (!valid_N(N) || S < 1) return MTG_ERR_INVALID_ARG;
   return (S - 1) + S * (N - 2) + 2 * S * (N - 2);

@@ -398,6 +398,25 @@ hipError_t launch_ragged_sample(int N, int D, int S_max, int64_t B, const int32_
 size_t ragged_extrema_lds_bytes(int N, int S_max, int D);
 size_t ragged_sample_lds_bytes(int N, int S_max, int D, int max_deriv);
 
+// Collision walk of a ragged batch (mtg_ragged_coll.hip): collision_cost_kernel
+// per row with the row's own count, the first colliding sample and a gate.
+// Every output is nullable; grad_coeffs null is the gate-only launch.
+struct RaggedCollOut {
+  double* cost;           // B
+  int32_t* collision;     // B: 0 / 1 (-1: bad count)
+  int32_t* hit_segment;   // B: segment of the first colliding sample, or -1
+  double* hit_time;       // B: its t within that segment, or NaN
+  double* grad_coeffs;    // B x S_max x 3 x N, 0.0 past the row's count
+  const double* gate_in;  // B; gate_out = gate_in on a free row, +inf on a
+  double* gate_out;       // colliding one (null: no gate; may alias)
+};
+hipError_t launch_ragged_collision(int N, int S_max, int64_t B, const int32_t* seg_counts,
+                                   const double* coeffs, const double* times, const float* occ,
+                                   int nx, int ny, int nz, const uint16_t* field,
+                                   const mtg_collision_params& p, const RaggedCollOut& out,
+                                   hipStream_t st);
+size_t ragged_collision_lds_bytes(int N, int S_max, bool grad);
+
 // Collision-driven objectives and their optimiser (mtg_coll_opt.hip); return
 // MTG_* codes.  All scratch comes from the caller's workspace.
 size_t coll_workspace_bytes(const PlanDev& pl, int64_t B, int mode, const mtg_coll_params& p,
