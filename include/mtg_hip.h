@@ -914,6 +914,63 @@ int mtg_ragged_collision_cost(int N, int S_max, int64_t B, const int32_t* seg_co
                               double* hit_time, double* grad_coeffs, const double* gate_in,
                               double* gate_out, void* stream);
 
+/* ------------------------------------------------------------------------
+ * Ragged tube QCQP: mtg_tube_solve and mtg_tube_residuals over rows with
+ * their own segment counts, in one launch each.  seg_counts B (int32, device,
+ * read by the kernels only, so a captured launch may be replayed over other
+ * counts), 2 <= S_b <= S_max.  With M = N / 2, all arrays on the device:
+ *   positions   B x (S_max+1) x 3   the first S_b + 1 vertices are read
+ *   fixed_vals  B x 3 x N           as mtg_tube_solve
+ *   times_cp    B x S_max           the first S_b are read
+ *   times       B x S_max           the first S_b are read
+ *   radii       B x S_max x 2       the first S_b are read
+ *   x           B x 3 x (S_max-1)M  row d: the (S_b-1) M values of dimension d
+ *                                   in the reference's order, then 0.0
+ *                                   (in for the residuals, nullable out for
+ *                                   the solve)
+ *   coeffs      B x S_max x 3 x N   segments >= S_b written 0.0: the layout
+ *                                   the ragged evaluators above read
+ *   resid       B x n_con(S_max)    the n_con(S_b) residuals in the
+ *                                   reference's order for S_b, then -inf, so
+ *                                   resid <= tol and a row maximum keep
+ *                                   their meaning
+ *   cost, iters, status  B          nullable, as mtg_tube_solve
+ * The padding of every input may be NaN and is never read.  Per row the
+ * results are those of mtg_tube_solve / mtg_tube_residuals on the row's first
+ * S_b segments (same IPM, same tolerances; not bitwise: mtg_tube_solve runs
+ * bodies compiled for one S).
+ *
+ * A row whose count is outside [2, S_max] gets MTG_TRAJ_BAD_SEGMENTS, a row
+ * with a non-positive time among its first S_b MTG_TRAJ_BAD_TIME: x and
+ * coeffs NaN over the whole padded row, cost NaN, iters 0, the resid row
+ * NaN; nothing outside the row is touched.
+ *
+ * order_ws (nullable): B int32 of caller-owned device memory.  Non-NULL: the
+ * call first sorts the rows into it by count, longest first, rows with a bad
+ * count last (one small launch), and the solve's workgroups take their rows
+ * from it in that order; afterwards it holds that permutation.  NULL: rows
+ * in index order.  Results do not depend on it.
+ *
+ * Checks, in this order: N, r, S_max >= 2, 0 <= B < 2^26 and
+ * B x S_max < 2^31 (MTG_ERR_INVALID_ARG), then the LDS of the largest layout
+ * of 2..S_max (MTG_ERR_UNSUPPORTED), all before ctx or any pointer is looked
+ * at; then NULL ctx, or a NULL required pointer with B > 0; then tol and
+ * max_iter positive.  B == 0 returns MTG_OK and launches nothing.  Neither
+ * call allocates or synchronises.
+ * mtg_ragged_tube_num_constraints(N, S_max) = mtg_tube_num_constraints. */
+int mtg_ragged_tube_num_constraints(int N, int S_max);
+int mtg_ragged_tube_residuals(mtg_ctx* ctx, int N, int r, int S_max, int64_t B,
+                              const int32_t* seg_counts, const double* positions,
+                              const double* fixed_vals, const double* times_cp,
+                              const double* times, const double* radii, const double* x,
+                              double* resid, void* stream);
+int mtg_ragged_tube_solve(mtg_ctx* ctx, int N, int r, int S_max, int64_t B,
+                          const int32_t* seg_counts, const double* positions,
+                          const double* fixed_vals, const double* times_cp,
+                          const double* times, const double* radii, double tol, int max_iter,
+                          double* x, double* coeffs, double* cost, int32_t* iters,
+                          int32_t* status, int32_t* order_ws, void* stream);
+
 int64_t mtg_coll_workspace_bytes(const mtg_plan* plan, int64_t B, int mode,
                                  const mtg_coll_params* params, int optimize);
 /* near_field: mtg_coll_field of the same occupancy and box_side, or NULL

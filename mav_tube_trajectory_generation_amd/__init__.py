@@ -12,8 +12,10 @@ from .batch import (Context, LinearPlan, RaggedLinearPlan, coll_field,  # noqa: 
                     generate_random_problems,
                     magnitude_candidates,
                     max_magnitude,
-                    min_max_magnitude, pack_ragged, ragged_collision_cost, ragged_max_magnitude,
+                    min_max_magnitude, pack_ragged, pack_ragged_tube, ragged_collision_cost,
+                    ragged_max_magnitude,
                     ragged_sample_trajectories, ragged_soft_constraint_cost,
+                    ragged_tube_num_constraints, ragged_tube_residuals, ragged_tube_solve,
                     sample_trajectories, segment_matrices,
                     soft_constraint_cost,
                     tube_num_constraints, tube_residuals, tube_solve, tube_time_cost,
@@ -26,6 +28,8 @@ __all__ = ["Context", "LinearPlan", "RaggedLinearPlan", "pack_ragged", "MTGError
            "min_max_magnitude", "make_coll_params", "make_collision_params", "make_time_params",
            "COLL_DEFAULTS",
            "ragged_collision_cost", "ragged_max_magnitude", "ragged_sample_trajectories", "ragged_soft_constraint_cost",
+           "pack_ragged_tube", "ragged_tube_num_constraints", "ragged_tube_residuals",
+           "ragged_tube_solve",
            "sample_trajectories", "segment_matrices", "soft_constraint_cost",
            "tube_num_constraints", "tube_residuals", "tube_solve", "tube_time_cost",
            "tube_time_optimize", "tube_time_workspace_bytes", "lib", "LIB_PATH"]

@@ -240,6 +240,14 @@ SIGNATURES = {
     "mtg_tube_solve": (ctypes.c_int, [_vp, ctypes.c_int, ctypes.c_int, ctypes.c_int,
                                       ctypes.c_int64, _vp, _vp, _vp, _vp, _vp, ctypes.c_double,
                                       ctypes.c_int, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "mtg_ragged_tube_num_constraints": (ctypes.c_int, [ctypes.c_int, ctypes.c_int]),
+    "mtg_ragged_tube_residuals": (ctypes.c_int, [_vp, ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                                                 ctypes.c_int64, _vp, _vp, _vp, _vp, _vp, _vp,
+                                                 _vp, _vp, _vp]),
+    "mtg_ragged_tube_solve": (ctypes.c_int, [_vp, ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                                             ctypes.c_int64, _vp, _vp, _vp, _vp, _vp, _vp,
+                                             ctypes.c_double, ctypes.c_int, _vp, _vp, _vp, _vp,
+                                             _vp, _vp, _vp]),
     "mtg_tube_time_workspace_bytes": (ctypes.c_int64, [ctypes.c_int, ctypes.c_int,
                                                        ctypes.c_int64,
                                                        ctypes.POINTER(TimeParams),

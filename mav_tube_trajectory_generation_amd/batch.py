@@ -893,6 +893,141 @@ def tube_solve(ctx, N, r, positions, fixed_vals, times_cp, times, radii, tol=1e-
     return dict(x=x, coeffs=coeffs, cost=cost, iters=iters, status=status)
 
 
+def _require_int32(t, shape, name):
+    import torch
+    if not isinstance(t, torch.Tensor) or not t.is_cuda:
+        raise MTGError(f"{name} must be a CUDA tensor")
+    if t.dtype != torch.int32:
+        raise MTGError(f"{name} must be int32")
+    if tuple(t.shape) != tuple(shape):
+        raise MTGError(f"{name} has shape {tuple(t.shape)}, expected {tuple(shape)}")
+    if not t.is_contiguous():
+        raise MTGError(f"{name} must be contiguous")
+
+
+def _ragged_tube_inputs(N, seg_counts, positions, fixed_vals, times_cp, times, radii):
+    import torch
+    if not isinstance(times, torch.Tensor) or times.dim() != 2:
+        raise MTGError("times must be a CUDA tensor [B, S_max]")
+    B, S_max = times.shape
+    for name, t, shp in (("times", times, (B, S_max)), ("times_cp", times_cp, (B, S_max)),
+                         ("positions", positions, (B, S_max + 1, 3)),
+                         ("fixed_vals", fixed_vals, (B, 3, N)),
+                         ("radii", radii, (B, S_max, 2))):
+        _require(t, shp, name)
+    _require_counts(seg_counts, B)
+    return B, S_max
+
+
+def ragged_tube_num_constraints(N, S_max):
+    return lib().mtg_ragged_tube_num_constraints(N, S_max)
+
+
+def ragged_tube_residuals(ctx, N, r, seg_counts, positions, fixed_vals, times_cp, times, radii,
+                          x):
+    """tube_residuals over a ragged batch in one launch
+    (mtg_ragged_tube_residuals): row b holds the residuals of the tube problem
+    of its first S_b = seg_counts[b] segments at x[b].
+
+    seg_counts [B] int32, positions [B, S_max + 1, 3], fixed_vals [B, 3, N],
+    times_cp and times [B, S_max], radii [B, S_max, 2], x [B, 3, (S_max - 1) M]
+    (CUDA), as pack_ragged_tube and ragged_tube_solve give them; the padding
+    is never read.  Returns resid [B, n_con(S_max)]: the row's n_con(S_b)
+    residuals, then -inf.  A row whose count is outside [2, S_max] or with a
+    non-positive time is NaN.  The counts stay on the device."""
+    import torch
+    B, S_max = _ragged_tube_inputs(N, seg_counts, positions, fixed_vals, times_cp, times, radii)
+    _require(x, (B, 3, (S_max - 1) * (N // 2)), "x")
+    dev = times.device
+    m = max(ragged_tube_num_constraints(N, S_max), 0)
+    resid = torch.empty((B, m), dtype=torch.float64, device=dev)
+    check(lib().mtg_ragged_tube_residuals(
+        ctx.handle, N, r, S_max, B, _ptr(seg_counts), _ptr(positions), _ptr(fixed_vals),
+        _ptr(times_cp), _ptr(times), _ptr(radii), _ptr(x), _ptr(resid), _stream(dev)),
+        "mtg_ragged_tube_residuals")
+    return resid
+
+
+def ragged_tube_solve(ctx, N, r, seg_counts, positions, fixed_vals, times_cp, times, radii,
+                      tol=1e-10, max_iter=100, order=True, out=None):
+    """tube_solve over a ragged batch in one launch (mtg_ragged_tube_solve):
+    row b is the tube QCQP of its first S_b = seg_counts[b] segments,
+    2 <= S_b <= S_max.  Inputs as ragged_tube_residuals.
+
+    Returns a dict of x [B, 3, (S_max - 1) M] (row d: (S_b - 1) M values, then
+    0.0), coeffs [B, S_max, 3, N] (segments >= S_b are 0.0: what the ragged
+    evaluators read), cost [B], iters [B] int32, status [B] int32; out may
+    supply any of them.  order=True sorts the rows by count on the device and
+    dispatches the longest first (the permutation is returned as order [B]
+    int32); the results do not depend on it.  A row whose count is out of
+    range (status 5) or with a non-positive time (status 1) has x, coeffs and
+    cost NaN and iters 0.  The counts stay on the device: a captured call may
+    be replayed over other counts."""
+    import torch
+    B, S_max = _ragged_tube_inputs(N, seg_counts, positions, fixed_vals, times_cp, times, radii)
+    dev = times.device
+    M = N // 2
+    out = dict(out) if out is not None else {}
+    shapes = {"x": (B, 3, (S_max - 1) * M), "coeffs": (B, S_max, 3, N), "cost": (B,)}
+    ints = ("iters", "status") + (("order",) if order else ())
+    for name, shp in shapes.items():  # the caller's outputs first, then the missing ones
+        if name in out:
+            _require(out[name], shp, name)
+    for name in ints:
+        if name in out:
+            _require_int32(out[name], (B,), name)
+    for name, shp in shapes.items():
+        if name not in out:
+            out[name] = torch.empty(shp, dtype=torch.float64, device=dev)
+    for name in ints:
+        if name not in out:
+            out[name] = torch.empty(B, dtype=torch.int32, device=dev)
+    check(lib().mtg_ragged_tube_solve(
+        ctx.handle, N, r, S_max, B, _ptr(seg_counts), _ptr(positions), _ptr(fixed_vals),
+        _ptr(times_cp), _ptr(times), _ptr(radii), float(tol), int(max_iter), _ptr(out["x"]),
+        _ptr(out["coeffs"]), _ptr(out["cost"]), _ptr(out["iters"]), _ptr(out["status"]),
+        _ptr(out["order"] if order else None), _stream(dev)), "mtg_ragged_tube_solve")
+    return out
+
+
+def pack_ragged_tube(problems, N, device, S_max=None):
+    """Padded inputs of ragged_tube_solve from a list of (positions
+    [S_b + 1, 3], fixed_vals [3, N], times [S_b], radii [S_b, 2]).  Returns
+    seg_counts [B] int32, positions [B, S_max + 1, 3], fixed_vals [B, 3, N],
+    times [B, S_max], radii [B, S_max, 2] on `device` (S_max None: the longest
+    count).  The padding of the float arrays is NaN: no kernel may read it,
+    and one that does shows."""
+    import torch
+    if not problems:
+        raise MTGError("pack_ragged_tube needs at least one problem")
+    probs = [(np.asarray(p, dtype=np.float64), np.asarray(f, dtype=np.float64),
+              np.asarray(t, dtype=np.float64).reshape(-1), np.asarray(rd, dtype=np.float64))
+             for p, f, t, rd in problems]
+    counts = np.array([t.size for _, _, t, _ in probs], dtype=np.int32)
+    S_max = int(counts.max()) if S_max is None else int(S_max)
+    if S_max < int(counts.max()):
+        raise MTGError(f"S_max = {S_max} is below the longest count {int(counts.max())}")
+    B = len(probs)
+    pos = np.full((B, S_max + 1, 3), np.nan)
+    fixed = np.full((B, 3, N), np.nan)
+    times = np.full((B, S_max), np.nan)
+    radii = np.full((B, S_max, 2), np.nan)
+    for b, (p, f, t, rd) in enumerate(probs):
+        S = t.size
+        if S < 2:
+            raise MTGError(f"problem {b}: a tube problem needs at least 2 segments, got {S}")
+        if p.shape != (S + 1, 3) or f.shape != (3, N) or rd.shape != (S, 2):
+            raise MTGError(f"problem {b}: shapes {p.shape}, {f.shape}, {rd.shape}, expected "
+                           f"{(S + 1, 3)}, {(3, N)}, {(S, 2)} for {S} segments")
+        pos[b, :S + 1] = p
+        fixed[b] = f
+        times[b, :S] = t
+        radii[b, :S] = rd
+    return (torch.from_numpy(counts).to(device), torch.from_numpy(pos).to(device),
+            torch.from_numpy(fixed).to(device), torch.from_numpy(times).to(device),
+            torch.from_numpy(radii).to(device))
+
+
 def _tube_geometry(N, positions, fixed_vals, radii, B, S):
     for name, t, shp in (("positions", positions, (B, S + 1, 3)),
                          ("fixed_vals", fixed_vals, (B, 3, N)), ("radii", radii, (B, S, 2))):

@@ -1187,6 +1187,67 @@ int mtg_tube_solve(mtg_ctx* ctx, int N, int r, int S, int64_t B, const double* p
                                          static_cast<hipStream_t>(stream)));
 }
 
+int mtg_ragged_tube_num_constraints(int N, int S_max) {
+  return mtg_tube_num_constraints(N, S_max);
+}
+
+// The ragged tube entries: the sizes first (they need neither a pointer nor a
+// device), the LDS for every count up to S_max checked here, not met as a
+// failure of the launch; then the pointers.  B == 0 needs no context.
+static int ragged_tube_args(mtg_ctx* ctx, int N, int r, int S_max, int64_t B,
+                            const int32_t* seg_counts, const double* positions,
+                            const double* fixed_vals, const double* times_cp,
+                            const double* times, const double* radii, mtg::RaggedTubeArgs* a) {
+  if (!valid_N(N) || r < 0 || r > N / 2 - 1 || S_max < 2 || !tube_grid_ok(S_max, B))
+    return MTG_ERR_INVALID_ARG;
+  if (mtg::ragged_tube_lds_bytes(N, S_max) > static_cast<size_t>(mtg::kMaxLdsBytes))
+    return MTG_ERR_UNSUPPORTED;
+  if (B && (!ctx || !seg_counts || !positions || !fixed_vals || !times_cp || !times || !radii))
+    return MTG_ERR_INVALID_ARG;
+  const double* tab = nullptr;
+  if (B) {
+    const int rc = get_tables(ctx, N, r, &tab);
+    if (rc) return rc;
+  }
+  *a = mtg::RaggedTubeArgs{N, r, S_max, B, seg_counts, tab, positions, fixed_vals, times_cp,
+                           times, radii};
+  return MTG_OK;
+}
+
+int mtg_ragged_tube_residuals(mtg_ctx* ctx, int N, int r, int S_max, int64_t B,
+                              const int32_t* seg_counts, const double* positions,
+                              const double* fixed_vals, const double* times_cp,
+                              const double* times, const double* radii, const double* x,
+                              double* resid, void* stream) {
+  clear_stale_error();
+  mtg::RaggedTubeArgs a;
+  const int rc = ragged_tube_args(ctx, N, r, S_max, B, seg_counts, positions, fixed_vals,
+                                  times_cp, times, radii, &a);
+  if (rc) return rc;
+  if (B && (!x || !resid)) return MTG_ERR_INVALID_ARG;
+  if (B == 0) return MTG_OK;
+  return from_hip(
+      mtg::launch_ragged_tube_residuals(a, x, resid, static_cast<hipStream_t>(stream)));
+}
+
+int mtg_ragged_tube_solve(mtg_ctx* ctx, int N, int r, int S_max, int64_t B,
+                          const int32_t* seg_counts, const double* positions,
+                          const double* fixed_vals, const double* times_cp,
+                          const double* times, const double* radii, double tol, int max_iter,
+                          double* x, double* coeffs, double* cost, int32_t* iters,
+                          int32_t* status, int32_t* order_ws, void* stream) {
+  clear_stale_error();
+  mtg::RaggedTubeArgs a;
+  const int rc = ragged_tube_args(ctx, N, r, S_max, B, seg_counts, positions, fixed_vals,
+                                  times_cp, times, radii, &a);
+  if (rc) return rc;
+  if (B && !coeffs) return MTG_ERR_INVALID_ARG;
+  if (!(tol > 0) || max_iter < 1) return MTG_ERR_INVALID_ARG;
+  if (B == 0) return MTG_OK;
+  return from_hip(mtg::launch_ragged_tube_solve(a, tol, max_iter, x, coeffs, cost, iters, status,
+                                                order_ws, static_cast<hipStream_t>(stream)));
+}
+
 static bool valid_tube_time_params(int N, int S, const mtg_time_params* p) {
   if (!p || p->n_soft < 0 || p->n_soft > mtg::kMaxSoftConstraints) return false;
   if (p->hard_constraints != 0) return false;

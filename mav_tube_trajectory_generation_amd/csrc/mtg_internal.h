@@ -225,6 +225,30 @@ int tube_time_optimize(const TubeArgs& a, double* times_io, double tol, int max_
                        int32_t* result, int32_t* status, void* workspace, size_t workspace_bytes,
                        hipStream_t st);
 
+// Tube QCQP of a ragged batch (mtg_ragged_tube.hip): mtg_tube_solve and
+// mtg_tube_residuals per row with the row's own count, rows padded to S_max.
+struct RaggedTubeArgs {
+  int N, r, S_max;
+  int64_t B;
+  const int32_t* seg_counts;  // B (device)
+  const double* tab;          // H(1), A(1)^-1 for (N, r)
+  const double* positions;    // B x (S_max+1) x 3
+  const double* fixed_vals;   // B x 3 x N
+  const double* times_cp;     // B x S_max
+  const double* times;        // B x S_max
+  const double* radii;        // B x S_max x 2
+};
+hipError_t launch_ragged_tube_residuals(const RaggedTubeArgs& a, const double* x, double* resid,
+                                        hipStream_t st);
+// order_ws non-null: B int32 the call sorts the rows into (longest first) and
+// dispatches through.
+hipError_t launch_ragged_tube_solve(const RaggedTubeArgs& a, double tol, int max_iter, double* x,
+                                    double* coeffs, double* cost, int32_t* iters,
+                                    int32_t* status, int32_t* order_ws, hipStream_t st);
+// LDS per workgroup: the largest layout of the counts 2..S_max (capped just
+// above kMaxLdsBytes).
+size_t ragged_tube_lds_bytes(int N, int S_max);
+
 constexpr int kMaxLdsBytes = 160 * 1024;
 
 // Launch helpers of the one-workgroup-per-problem kernels.

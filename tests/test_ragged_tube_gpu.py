@@ -1,0 +1,398 @@
+"""The tube QCQP of a ragged batch on the GPU (mtg_ragged_tube_solve /
+mtg_ragged_tube_residuals) against the oracle per row, against the uniform
+entry, and its padding, bad-row, ordering, graph-replay and chaining rules.
+
+Tolerances are those of tests/test_tube_gpu.py.  Every row of every parity
+case is compared: the oracle's status is asserted to be 0, no row is left out.
+The padding of every input is NaN.
+"""
+import ctypes
+import functools
+
+import numpy as np
+import pytest
+
+import pyoracle
+from helpers import rel_err, rel_err_coeffs
+
+pytestmark = pytest.mark.gpu
+
+torch = pytest.importorskip("torch")
+
+BAD_TIME, BAD_SEGMENTS = 1, 5
+RADIUS = 0.15
+CASE1 = dict(n=10, r=4, S_max=6, rows=tuple((S, 500 + b) for b, S in enumerate([2, 3, 6, 4, 2, 5])))
+
+
+@functools.lru_cache(maxsize=None)
+def problem(n, S, seed, scale=1.0):
+    """Row inputs: random_vertices(M - 1, S, 3, -10, 10, seed), control-point
+    times estimate_segment_times(v, 3, 5), segment times scale x those."""
+    m = n // 2
+    v = pyoracle.random_vertices(m - 1, S, 3, -10.0, 10.0, seed)
+    t0 = pyoracle.estimate_segment_times(v, 3.0, 5.0)
+    fv = np.zeros((3, n))
+    fv[:, :m] = v.vals[0, :m, :].T
+    fv[:, m:] = v.vals[S, :m, :].T
+    return dict(v=v, S=S, pos=v.vals[:, 0, :].copy(), fv=fv, t=t0 * scale, tcp=t0,
+                radii=np.full((S, 2), RADIUS))
+
+
+@functools.lru_cache(maxsize=None)
+def reference(n, r, S, seed, scale=1.0):
+    """The oracle's solve of a row, computed once and shared."""
+    p = problem(n, S, seed, scale)
+    ref = pyoracle.tube_solve(n, r, p["v"], p["t"], p["radii"], times_cp=p["tcp"], tol=1e-10,
+                              max_iter=100)
+    assert ref["status"] == 0, (n, r, S, seed, scale, ref["status"])
+    return ref
+
+
+def padded(n, S_max, rows, dev):
+    """Padded device inputs of a batch.  rows: problem() dicts, or an int for a
+    row that is not a trajectory (that count, every value NaN)."""
+    B = len(rows)
+    a = dict(seg_counts=np.zeros(B, np.int32), positions=np.full((B, S_max + 1, 3), np.nan),
+             fixed_vals=np.full((B, 3, n), np.nan), times_cp=np.full((B, S_max), np.nan),
+             times=np.full((B, S_max), np.nan), radii=np.full((B, S_max, 2), np.nan))
+    for b, p in enumerate(rows):
+        if isinstance(p, int):
+            a["seg_counts"][b] = p
+            continue
+        S = p["S"]
+        a["seg_counts"][b] = S
+        a["positions"][b, :S + 1] = p["pos"]
+        a["fixed_vals"][b] = p["fv"]
+        a["times_cp"][b, :S] = p["tcp"]
+        a["times"][b, :S] = p["t"]
+        a["radii"][b, :S] = p["radii"]
+    return {k: torch.from_numpy(v).to(dev) for k, v in a.items()}
+
+
+def solve(ctx, n, r, inp, **kw):
+    import mav_tube_trajectory_generation_amd as mtg
+    out = mtg.ragged_tube_solve(ctx, n, r, **inp, **kw)
+    torch.cuda.synchronize()
+    return out
+
+
+def host(out):
+    return {k: v.cpu().numpy() for k, v in out.items()}
+
+
+def same_bits(a, b):
+    a, b = np.ascontiguousarray(a), np.ascontiguousarray(b)
+    return a.shape == b.shape and a.dtype == b.dtype and a.tobytes() == b.tobytes()
+
+
+def check_rows(ctx, n, r, S_max, specs, inp, out):
+    """Every row of `out` against the oracle: status, x, coeffs, cost, iters,
+    feasibility and the exact padding."""
+    import mav_tube_trajectory_generation_amd as mtg
+    m = n // 2
+    res = mtg.ragged_tube_residuals(ctx, n, r, x=out["x"], **inp).cpu().numpy()
+    o = host(out)
+    assert o["x"].shape == (len(specs), 3, (S_max - 1) * m)
+    assert o["coeffs"].shape == (len(specs), S_max, 3, n)
+    assert res.shape == (len(specs), mtg.ragged_tube_num_constraints(n, S_max))
+    for b, (S, seed, *scale) in enumerate(specs):
+        ref = reference(n, r, S, seed, *scale)
+        row = (S - 1) * m
+        ncon = mtg.tube_num_constraints(n, S)
+        e_x = rel_err_coeffs(o["x"][b, :, :row], np.asarray(ref["x"]).reshape(3, row))
+        e_c = rel_err_coeffs(o["coeffs"][b, :S], ref["coeffs"])
+        e_j = rel_err(o["cost"][b], ref["cost"])
+        worst = res[b, :ncon].max()
+        print(f"N={n} row {b} S={S}: status {o['status'][b]} iters {o['iters'][b]} "
+              f"(oracle {ref['iters']}) x {e_x:.2e} coeffs {e_c:.2e} cost {e_j:.2e} "
+              f"resid {worst:.2e}")
+        assert o["status"][b] == 0, b
+        assert e_x <= 1e-6, b
+        assert e_c <= 1e-6, b
+        assert e_j <= 1e-6, b
+        assert abs(int(o["iters"][b]) - ref["iters"]) <= 2, b
+        assert worst <= 1e-8, b
+        assert same_bits(o["x"][b, :, row:], np.zeros((3, (S_max - 1) * m - row))), b
+        assert same_bits(o["coeffs"][b, S:], np.zeros((S_max - S, 3, n))), b
+        assert np.all(np.isneginf(res[b, ncon:])), b
+
+
+@pytest.fixture(scope="module")
+def case1(ctx, dev):
+    """Case 1's batch, solved once (dispatch order on) and left unchanged."""
+    c = CASE1
+    inp = padded(c["n"], c["S_max"], [problem(c["n"], S, seed) for S, seed in c["rows"]], dev)
+    return inp, solve(ctx, c["n"], c["r"], inp)
+
+
+def test_parity(ctx, case1):
+    c = CASE1
+    inp, out = case1
+    check_rows(ctx, c["n"], c["r"], c["S_max"], c["rows"], inp, out)
+
+
+@pytest.mark.parametrize("n,r", [(4, 1), (6, 2), (8, 3), (12, 5)])
+def test_every_order(ctx, dev, n, r):
+    """Both lane organisations of the block solves (BS <= 16 row-split, the
+    one-wave N = 12) and both launch shapes."""
+    specs = [(S, 600 + 7 * n + b) for b, S in enumerate([2, 4, 3])]
+    inp = padded(n, 4, [problem(n, S, seed) for S, seed in specs], dev)
+    check_rows(ctx, n, r, 4, specs, inp, solve(ctx, n, r, inp))
+
+
+def test_s_max_above_every_count(ctx, dev):
+    """The row's layout carved inside a larger allocation, strides of S_max."""
+    specs = [(S, 700 + b) for b, S in enumerate([3, 5, 2, 4])]
+    inp = padded(10, 12, [problem(10, S, seed) for S, seed in specs], dev)
+    check_rows(ctx, 10, 4, 12, specs, inp, solve(ctx, 10, 4, inp))
+
+
+def test_stale_control_point_times(ctx, dev):
+    """times = 0.9 t0 with the control-point maps at t0 (qcqp_impl:152-157)."""
+    specs = [(3, 801, 0.9), (5, 802, 0.9), (2, 803, 0.9)]
+    inp = padded(10, 5, [problem(10, S, seed, sc) for S, seed, sc in specs], dev)
+    assert not torch.equal(inp["times"][0, :3], inp["times_cp"][0, :3])
+    check_rows(ctx, 10, 4, 5, specs, inp, solve(ctx, 10, 4, inp))
+
+
+def test_against_uniform_entry(ctx, dev, case1):
+    """Case 1's rows through tube_solve per S: equal statuses, values within
+    the parity tolerances (another translation unit and, at N = 10, another
+    body: not bitwise)."""
+    import mav_tube_trajectory_generation_amd as mtg
+    c = CASE1
+    n, r, m = c["n"], c["r"], c["n"] // 2
+    o = host(case1[1])
+    T = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)  # noqa: E731
+    seen = 0
+    for S in sorted({S for S, _ in c["rows"]}):
+        idx = [b for b, (Sb, _) in enumerate(c["rows"]) if Sb == S]
+        ps = [problem(n, S, c["rows"][b][1]) for b in idx]
+        u = host(mtg.tube_solve(ctx, n, r, T(np.stack([p["pos"] for p in ps])),
+                                T(np.stack([p["fv"] for p in ps])),
+                                T(np.stack([p["tcp"] for p in ps])),
+                                T(np.stack([p["t"] for p in ps])),
+                                T(np.stack([p["radii"] for p in ps])), tol=1e-10, max_iter=100))
+        for k, b in enumerate(idx):
+            seen += 1
+            assert o["status"][b] == u["status"][k], b
+            assert abs(int(o["iters"][b]) - int(u["iters"][k])) <= 2, b
+            assert rel_err_coeffs(o["x"][b, :, :(S - 1) * m],
+                                  u["x"][k].reshape(3, (S - 1) * m)) <= 1e-6, b
+            assert rel_err_coeffs(o["coeffs"][b, :S], u["coeffs"][k]) <= 1e-6, b
+            assert rel_err(o["cost"][b], u["cost"][k]) <= 1e-6, b
+    assert seen == len(c["rows"])
+
+
+def test_residuals_match_oracle(ctx, dev):
+    """Residuals at arbitrary x, times_cp != times, in the reference's order
+    for the row's own S; the padding exactly -inf.  x's padding is NaN."""
+    import mav_tube_trajectory_generation_amd as mtg
+    c = CASE1
+    n, r, m, S_max = c["n"], c["r"], c["n"] // 2, c["S_max"]
+    rng = np.random.default_rng(6)
+    ps = [problem(n, S, seed, 0.9) for S, seed in c["rows"]]
+    inp = padded(n, S_max, ps, dev)
+    x = np.full((len(ps), 3, (S_max - 1) * m), np.nan)
+    xs = []
+    for b, p in enumerate(ps):
+        xs.append(rng.normal(size=(3, (p["S"] - 1) * m)))
+        x[b, :, :xs[b].shape[1]] = xs[b]
+    got = mtg.ragged_tube_residuals(ctx, n, r, x=torch.from_numpy(x).to(dev), **inp).cpu().numpy()
+    assert got.shape == (len(ps), mtg.ragged_tube_num_constraints(n, S_max))
+    for b, p in enumerate(ps):
+        ref = pyoracle.tube_residuals(n, r, p["v"], p["t"], p["radii"], xs[b].reshape(-1),
+                                      times_cp=p["tcp"])
+        ncon = mtg.tube_num_constraints(n, p["S"])
+        assert ref.shape == (ncon,)
+        err = np.max(np.abs(got[b, :ncon] - ref) / np.maximum(1.0, np.abs(ref)))
+        print(f"row {b} S={p['S']}: residual error {err:.2e}")
+        assert err <= 1e-10, b
+        assert np.all(np.isneginf(got[b, ncon:])), b
+
+
+def bad_batch(dev):
+    """Case 1's valid rows interleaved with counts 0, 1, S_max + 1 and -3."""
+    c = CASE1
+    ps = [problem(c["n"], S, seed) for S, seed in c["rows"]]
+    rows = [ps[0], 0, ps[1], 1, ps[2], c["S_max"] + 1, ps[3], -3, ps[4], ps[5]]
+    valid = [b for b, p in enumerate(rows) if not isinstance(p, int)]
+    return padded(c["n"], c["S_max"], rows, dev), valid
+
+
+def poisoned(B, n, S_max, dev, order=True):
+    """An output set filled with a value no solve writes."""
+    m = n // 2
+    out = {"x": torch.full((B, 3, (S_max - 1) * m), 777.0, dtype=torch.float64, device=dev),
+           "coeffs": torch.full((B, S_max, 3, n), 777.0, dtype=torch.float64, device=dev),
+           "cost": torch.full((B,), 777.0, dtype=torch.float64, device=dev),
+           "iters": torch.full((B,), 777, dtype=torch.int32, device=dev),
+           "status": torch.full((B,), 777, dtype=torch.int32, device=dev)}
+    if order:
+        out["order"] = torch.full((B,), 777, dtype=torch.int32, device=dev)
+    return out
+
+
+def test_bad_rows(ctx, dev, case1):
+    import mav_tube_trajectory_generation_amd as mtg
+    c = CASE1
+    n, r, S_max = c["n"], c["r"], c["S_max"]
+    base = host(case1[1])
+    inp, valid = bad_batch(dev)
+    B = inp["seg_counts"].numel()
+    o = host(solve(ctx, n, r, inp, out=poisoned(B, n, S_max, dev)))
+    res = mtg.ragged_tube_residuals(ctx, n, r, x=torch.from_numpy(o["x"]).to(dev),
+                                    **inp).cpu().numpy()
+    ref_res = mtg.ragged_tube_residuals(ctx, n, r, x=case1[1]["x"], **case1[0]).cpu().numpy()
+    for b in range(B):
+        if b in valid:
+            k = valid.index(b)  # bitwise the launch that holds only the valid rows
+            for name in ("x", "coeffs", "cost", "iters", "status"):
+                assert same_bits(o[name][b], base[name][k]), (b, name)
+            assert same_bits(res[b], ref_res[k]), b
+        else:
+            assert o["status"][b] == BAD_SEGMENTS and o["iters"][b] == 0, b
+            assert np.isnan(o["x"][b]).all() and np.isnan(o["coeffs"][b]).all(), b
+            assert np.isnan(o["cost"][b]) and np.isnan(res[b]).all(), b
+
+    # A zero time inside a row's first S_b: that row alone is BAD_TIME.
+    zt = {k: v.clone() for k, v in case1[0].items()}
+    zt["times"][2, 1] = 0.0
+    o = host(solve(ctx, n, r, zt, out=poisoned(len(c["rows"]), n, S_max, dev)))
+    res = mtg.ragged_tube_residuals(ctx, n, r, x=case1[1]["x"], **zt).cpu().numpy()
+    for b in range(len(c["rows"])):
+        if b == 2:
+            assert o["status"][b] == BAD_TIME and o["iters"][b] == 0
+            assert np.isnan(o["x"][b]).all() and np.isnan(o["coeffs"][b]).all()
+            assert np.isnan(o["cost"][b]) and np.isnan(res[b]).all()
+        else:
+            for name in ("x", "coeffs", "cost", "iters", "status"):
+                assert same_bits(o[name][b], base[name][b]), (b, name)
+            assert same_bits(res[b], ref_res[b]), b
+
+    # A zero or negative time in the padding changes nothing.
+    pt = {k: v.clone() for k, v in case1[0].items()}
+    pt["times"][0, 3] = 0.0      # S_0 = 2
+    pt["times"][1, 5] = -1.0     # S_1 = 3
+    pt["times_cp"][3, 4] = 0.0   # S_3 = 4
+    pt["times_cp"][4, 2] = -2.0  # S_4 = 2
+    o = host(solve(ctx, n, r, pt))
+    for name in ("x", "coeffs", "cost", "iters", "status"):
+        assert same_bits(o[name], base[name]), name
+    assert same_bits(mtg.ragged_tube_residuals(ctx, n, r, x=case1[1]["x"], **pt).cpu().numpy(),
+                     ref_res)
+
+
+def test_dispatch_order(ctx, dev):
+    """With and without order_ws: the same bits; order_ws afterwards is a
+    permutation, valid counts non-increasing, invalid rows last."""
+    c = CASE1
+    n, r, S_max = c["n"], c["r"], c["S_max"]
+    inp, valid = bad_batch(dev)
+    B = inp["seg_counts"].numel()
+    a = host(solve(ctx, n, r, inp, order=True))
+    b = host(solve(ctx, n, r, inp, order=False))
+    assert "order" in a and "order" not in b
+    for name in ("x", "coeffs", "cost", "iters", "status"):
+        assert same_bits(a[name], b[name]), name
+    order = a["order"]
+    assert sorted(order.tolist()) == list(range(B))
+    counts = inp["seg_counts"].cpu().numpy()[order]
+    ok = (counts >= 2) & (counts <= S_max)
+    assert ok[:len(valid)].all() and not ok[len(valid):].any()
+    assert np.all(np.diff(counts[:len(valid)]) <= 0)
+
+
+def test_graph_replay(ctx, dev):
+    """One captured call replayed over other counts and inputs, written in
+    place: the bits of a fresh eager call."""
+    import mav_tube_trajectory_generation_amd as mtg
+    c = CASE1
+    n, r, S_max = c["n"], c["r"], c["S_max"]
+    first = padded(n, S_max, [problem(n, S, seed) for S, seed in c["rows"]], dev)
+    ps = [problem(n, S, seed) for S, seed in c["rows"]]
+    second = padded(n, S_max, [ps[2], ps[0], 9, ps[5], ps[3], ps[1]], dev)
+    B = len(c["rows"])
+    out = poisoned(B, n, S_max, dev)
+    solve(ctx, n, r, first, out=out)  # warm-up: module load
+    g = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(g):
+        mtg.ragged_tube_solve(ctx, n, r, **first, out=out)
+    for k in first:
+        first[k].copy_(second[k])
+    g.replay()
+    torch.cuda.synchronize()
+    fresh = host(solve(ctx, n, r, second, out=poisoned(B, n, S_max, dev)))
+    got = host(out)
+    assert got["status"].tolist() == [0, 0, BAD_SEGMENTS, 0, 0, 0]
+    for name in ("x", "coeffs", "cost", "iters", "status"):
+        assert same_bits(got[name], fresh[name]), name
+
+
+def test_edges(ctx, dev):
+    import mav_tube_trajectory_generation_amd as mtg
+    n, r, m = 10, 4, 5
+    # B = 0: nothing to do, empty outputs
+    empty = padded(n, 4, [], dev)
+    out = solve(ctx, n, r, empty)
+    assert out["x"].shape == (0, 3, 3 * m) and out["coeffs"].shape == (0, 4, 3, n)
+    assert mtg.ragged_tube_residuals(ctx, n, r, x=out["x"], **empty).shape == (
+        0, mtg.ragged_tube_num_constraints(n, 4))
+    # B = 1, and S_max = 2 where every row has S = 2; the poisoned outputs are
+    # overwritten over their whole documented region
+    for specs, S_max in (([(3, 501)], 4), ([(2, 500), (2, 504)], 2)):
+        inp = padded(n, S_max, [problem(n, S, seed) for S, seed in specs], dev)
+        out = solve(ctx, n, r, inp, out=poisoned(len(specs), n, S_max, dev))
+        o = host(out)
+        for name in ("x", "coeffs", "cost", "iters", "status", "order"):
+            assert not np.any(o[name] == 777), name
+            assert not np.isnan(o[name]).any(), name
+        check_rows(ctx, n, r, S_max, specs, inp, out)
+        # without the nullable outputs: the same coefficients
+        c_only = torch.full_like(out["coeffs"], 777.0)
+        from mav_tube_trajectory_generation_amd import lib
+        from mav_tube_trajectory_generation_amd._abi import check
+        from mav_tube_trajectory_generation_amd.batch import _ptr, _stream
+        check(lib().mtg_ragged_tube_solve(
+            ctx.handle, n, r, S_max, len(specs), _ptr(inp["seg_counts"]), _ptr(inp["positions"]),
+            _ptr(inp["fixed_vals"]), _ptr(inp["times_cp"]), _ptr(inp["times"]),
+            _ptr(inp["radii"]), 1e-10, 100, None, _ptr(c_only), None, None, None, None,
+            _stream(dev)), "mtg_ragged_tube_solve")
+        torch.cuda.synchronize()
+        assert same_bits(c_only.cpu().numpy(), o["coeffs"])
+
+
+def test_chain(ctx, dev, case1):
+    """The evaluators read the ragged tube output as it is: the maximum speed
+    per row equals max_magnitude on the row's own slice, and the gated soft
+    cost followed by mtg_select_local picks the row a host computation picks."""
+    import mav_tube_trajectory_generation_amd as mtg
+    from mav_tube_trajectory_generation_amd import lib
+    from mav_tube_trajectory_generation_amd._abi import check
+    c = CASE1
+    inp, out = case1
+    seg, times, coeffs = inp["seg_counts"], inp["times"], out["coeffs"]
+    B = seg.numel()
+    rag = host(mtg.ragged_max_magnitude(seg, coeffs, times, derivative=1))
+    vmax = np.zeros(B)
+    for b, (S, _) in enumerate(c["rows"]):
+        one = host(mtg.max_magnitude(coeffs[b:b + 1, :S].contiguous(),
+                                     times[b:b + 1, :S].contiguous(), 1))
+        for name in ("time", "value", "segment"):
+            assert same_bits(rag[name][b:b + 1], one[name]), (b, name)
+        vmax[b] = one["value"][0]
+    # A speed limit halfway between the two middle maxima: both classes exist
+    # and no maximum is within rounding of the limit.
+    srt = np.sort(vmax)
+    limit = 0.5 * (srt[B // 2 - 1] + srt[B // 2])
+    soft = mtg.ragged_soft_constraint_cost(seg, coeffs, times, [1], [limit], gate=out["cost"])
+    triple = torch.empty(3, dtype=torch.float64, device=dev)
+    stream = ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+    check(lib().mtg_select_local(ctypes.c_void_p(soft["gated"].data_ptr()), B, 0, 0,
+                                 ctypes.c_void_p(triple.data_ptr()), stream), "mtg_select_local")
+    cost = out["cost"].cpu().numpy()
+    feasible = vmax <= limit
+    assert feasible.any() and not feasible.all()
+    want = int(np.argmin(np.where(feasible, cost, np.inf)))
+    got = triple.cpu().numpy()
+    assert (got[0], int(got[1]), int(got[2])) == (cost[want], want, 0)
