@@ -90,6 +90,13 @@ __device__ inline int64_t xcd_problem(int64_t i, int64_t G) {
   const int64_t x = i % kXcds, k = i / kXcds;
   return x * q + (x < r ? x : r) + k;
 }
+// The same bijection for a grid that fits 32 bits: shifts and masks on
+// scalar registers, no 64-bit compare, multiply or carry chain.
+__device__ inline unsigned xcd_problem32(unsigned i, unsigned G) {
+  const unsigned q = G / kXcds, r = G % kXcds;
+  const unsigned x = i % kXcds, k = i / kXcds;
+  return x * q + (x < r ? x : r) + k;
+}
 
 // Copy NCH 16-byte pieces of a staged output from LDS to global memory, lane
 // t of a group of W lanes taking pieces t, t + W, ...: consecutive lanes

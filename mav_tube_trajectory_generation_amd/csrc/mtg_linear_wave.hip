@@ -27,6 +27,12 @@ static_assert(kWpb >= 1 && kWpb <= 4, "1 to 4 waves per workgroup");
 #ifndef MTG_WAVE_T_DIRECT
 #define MTG_WAVE_T_DIRECT 1
 #endif
+// A/B builds of the entry change (5.1.1a): -DMTG_WAVE_ENTRY32=0 restores the
+// 64-bit problem index and offsets, the masked input stores and the inline
+// bad-time fills.
+#ifndef MTG_WAVE_ENTRY32
+#define MTG_WAVE_ENTRY32 1
+#endif
 
 // The problem count nb is an argument in the first 64 bytes (the first 56
 // are preloaded into SGPRs; nb is the one scalar load before the first
@@ -46,23 +52,36 @@ __global__ __launch_bounds__(kWave * kWpb) void linear_wave_kernel(
   using G = typename Sv::G;
   constexpr int MF = G::MF, MP = G::MP, NFIX = G::NFIX;
   __shared__ __attribute__((aligned(16))) double sm[kWpb * G::L_N];
+#if MTG_WAVE_ENTRY32
+  // nb is an int: the problem index and the row offsets in 32-bit scalar
+  // arithmetic (32 x 32 -> 64-bit products for the offsets, no 64-bit
+  // division, compare or carry chain ahead of the first load).
+  const unsigned nblk = (static_cast<unsigned>(nb) + kWpb - 1) / kWpb;
+#else
   const int nblk = (nb + kWpb - 1) / kWpb;
+#endif
   // The deferred selection (the previous step's costs) in one extra
   // workgroup after the solves: it runs beside them (about 1 us at
   // B = 1024 against a 3.4 us solve), so it costs no launch of its own.
-  if (kPrev && static_cast<int>(blockIdx.x) == nblk) {
+  if (kPrev && blockIdx.x == static_cast<unsigned>(nblk)) {
     if (threadIdx.x < kWave)
       select_reduce_block<kWave>(sel.prev_cost, sel.prev_count, sel.prev_start, sel.rank,
                                  sel.prev_out, nullptr, nullptr);
     return;
   }
   const int w = kWpb > 1 ? __builtin_amdgcn_readfirstlane(threadIdx.x / kWave) : 0;
+#if MTG_WAVE_ENTRY32
+  const unsigned b32 = xcd_problem32(blockIdx.x, nblk) * kWpb + w;
+  if (kWpb > 1 && b32 >= static_cast<unsigned>(nb)) return;
+  const uint64_t b = b32;
+#else
   const int64_t b = xcd_problem(blockIdx.x, nblk) * kWpb + w;
   if (kWpb > 1 && b >= nb) return;
+#endif
   Sv sv;
   sv.init(sm + w * G::L_N);
   const int lane = sv.lane;
-  const double* fb = fixed_vals + b * D * NFIX;
+  const double* fb = fixed_vals + b * (D * NFIX);
   const double* tb = times + b * S;
   MTG_STAMP(0);
   // Inputs: each value loaded from HBM by one lane only (the four waves of a
@@ -78,19 +97,27 @@ __global__ __launch_bounds__(kWave * kWpb) void linear_wave_kernel(
   // through the LDS copy the later phases use.
   [[maybe_unused]] double tl = 0.0, tr = 0.0;
   if constexpr (MTG_WAVE_T_DIRECT) {
-    tl = tb[sv.tl_index()];
-    tr = tb[sv.av];
+    tl = tb[static_cast<unsigned>(sv.tl_index())];
+    tr = tb[static_cast<unsigned>(sv.av)];
   }
   const double2 h_own = *reinterpret_cast<const double2*>(tab + 2 * (lane < N * N / 2 ? lane : 0));
   double* T = sv.aux();
+#if MTG_WAVE_ENTRY32
+  // every lane stores (spare lanes to the junk area): no execution-mask
+  // region between the loads and the solve, and none a load could sink into
+  sv.store_inputs_all(f0, f1, h_own, t_own, T);
+#else
   sv.store_constants(f0, f1, h_own);
   if (lane < S) T[lane] = t_own;
+#endif
   lds_order();
   const bool bad = __any(lane < S && (!(t_own > 0.0) || !(t_own < 1e300)));
   MTG_STAMP(7);
   constexpr int64_t per = static_cast<int64_t>(S) * D * N;
   constexpr int NP = (S - 1) * MF;
-  if (bad) {
+  // (unlikely: the fills are laid out after the solve, which is the
+  // fall-through)
+  if (MTG_WAVE_ENTRY32 ? __builtin_expect(bad, 0) : bad) {
     for (int i = lane; i < per; i += kWave) coeffs[b * per + i] = NAN;
     if (free_vals)
       for (int i = lane; i < D * NP; i += kWave) free_vals[b * D * NP + i] = NAN;

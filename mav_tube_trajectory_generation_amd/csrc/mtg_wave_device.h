@@ -206,15 +206,16 @@ struct Solver {
   // Fixed value i of d_f (D x NFIX, the standard order of linear_impl:171-252:
   // vertex 0 derivatives 0..M-1, intermediate positions, vertex S
   // derivatives 0..M-1) into dv[v][d][k].
-  __device__ void put_fixed(int i, double val) {
+  __device__ double* fixed_slot(int i) const {
     int d = 0;
 #pragma unroll
     for (int d2 = 1; d2 < D; ++d2) d += i >= d2 * NFIX ? 1 : 0;
     const int f = i - d * NFIX;
     const int v = f < M ? 0 : (f < M + S - 1 ? f - M + 1 : S);
     const int k = f < M ? f : (f < M + S - 1 ? 0 : f - (M + S - 1));
-    dv[(v * D + d) * MP + k] = val;
+    return dv + (v * D + d) * MP + k;
   }
+  __device__ void put_fixed(int i, double val) { *fixed_slot(i) = val; }
 
   // The per-trajectory constants into LDS: d_f (fb, D x NFIX) into dv and
   // H(1) (tab) into hh, one global load per lane each.  Caller orders LDS
@@ -233,6 +234,19 @@ struct Solver {
     if constexpr (D * NFIX > kWave)
       if (lane + kWave < D * NFIX) put_fixed(lane + kWave, f1);
     if (lane < N * N / 2) *reinterpret_cast<double2*>(hh + 2 * lane) = h_own;
+  }
+
+  // The same and the segment time t_own into T[lane] without an execution
+  // mask: every lane stores, a lane with nothing to hand out to the junk area
+  // (as the sweep's spare lanes do), so the values' loads cannot be sunk
+  // behind a branch either.
+  __device__ void store_inputs_all(double f0, double f1, double2 h_own, double t_own, double* T) {
+    static_assert(G::NJUNK >= 16, "junk words 8 .. 13");
+    *(lane < D * NFIX ? fixed_slot(lane) : junk + 8) = f0;
+    if constexpr (D * NFIX > kWave)
+      *(lane + kWave < D * NFIX ? fixed_slot(lane + kWave) : junk + 8) = f1;
+    *reinterpret_cast<double2*>(lane < N * N / 2 ? hh + 2 * lane : junk + 10) = h_own;
+    *(lane < S ? T + lane : junk + 12) = t_own;
   }
 
   // A solve at the segment times T (LDS, S valid values): dv receives every
