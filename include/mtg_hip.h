@@ -971,6 +971,71 @@ int mtg_ragged_tube_solve(mtg_ctx* ctx, int N, int r, int S_max, int64_t B,
                           double* x, double* coeffs, double* cost, int32_t* iters,
                           int32_t* status, int32_t* order_ws, void* stream);
 
+/* ------------------------------------------------------------------------
+ * Ragged tube QCQP time objective: mtg_tube_time_cost and
+ * mtg_tube_time_optimize_ex (LN_SBPLX) over rows with their own segment
+ * counts, one call for the whole batch.  seg_counts and the geometry are laid
+ * out as for mtg_ragged_tube_solve; the time arrays are rows of S_max:
+ *   times_cp, times, times_io, grad  B x S_max   the first S_b are read
+ * The padding of every input may be NaN and is never read.  grad entries
+ * >= S_b are written 0.0; times_io entries >= S_b keep their bits.
+ *
+ * Per row the results are those of the uniform entries at S = S_b:
+ * J = computeCost() of the QCQP at `times` + time_penalty (sum_{i<S_b} T_i)^2
+ * [+ soft]; grad_mode 0 or 2 (central differences with the 0.1 clamp, 2 S_b
+ * extra QCQP solves of the row, all in the same launch), grad_mode 1 is
+ * MTG_ERR_UNSUPPORTED.  The optimiser is LN_SBPLX (params->optimizer 1) with
+ * bounds [0.1, 2 T0], steps initial_stepsize_rel T0, ftol f_rel / f_abs and
+ * max_evals as maxeval; the first S_b entries of times_io are the initial
+ * times and the control-point times (copied to the workspace before the first
+ * write), every solve warm-starts from the row's previous one, result is the
+ * nlopt_result code and status the QCQP status of the first evaluation.
+ * params->optimizer 0 (the finite-difference descent of the uniform entry) is
+ * MTG_ERR_UNSUPPORTED here.  hard_constraints != 0 is MTG_ERR_INVALID_ARG, as
+ * in the uniform entries.
+ *
+ * The host never reads the counts.  A row whose count is outside [2, S_max]
+ * gets status MTG_TRAJ_BAD_SEGMENTS and cost NaN; the cost entry writes its
+ * grad NaN over the whole padded row, the optimiser gives it evals 0,
+ * result -1 and leaves its times untouched.  An initial time below 0.1 is
+ * NLopt's invalid start, as in the uniform entry: result -1, evals 0, cost
+ * NaN, times unchanged.  Either kind of row touches nothing outside itself.
+ *
+ * Scratch: `workspace` is a caller-owned device buffer of at least
+ * mtg_ragged_tube_time_workspace_bytes(N, S_max, B, params, optimize) bytes
+ * (optimize = 0 for the cost entry, 1 for the optimiser, with the same
+ * params); every word of it is written by the call before it is read.  No
+ * call allocates or synchronises, so each can be captured in a HIP graph and
+ * replayed over other counts, times and geometry.
+ *
+ * Checks, in this order: N, r, S_max >= 2, 0 <= B < 2^26 and B x S_max < 2^31
+ * (MTG_ERR_INVALID_ARG); S_max <= 64 and the LDS of the largest layout of
+ * 2..S_max (MTG_ERR_UNSUPPORTED); params (NULL, soft constraints,
+ * hard_constraints, increment: MTG_ERR_INVALID_ARG; grad_mode 1 or
+ * optimizer 0: MTG_ERR_UNSUPPORTED); B x P_max problems, P_max = 2 S_max + 1
+ * with grad_mode 2 and 1 otherwise, within 2^26 (MTG_ERR_INVALID_ARG); tol,
+ * max_iter and max_evals positive; all before ctx or any pointer is looked
+ * at.  Then NULL ctx or a NULL required pointer with B > 0.  B == 0 returns
+ * MTG_OK and launches nothing; a NULL or too small workspace is
+ * MTG_ERR_INVALID_ARG.  The query returns the (negative) code of the first
+ * failed size or parameter check. */
+int64_t mtg_ragged_tube_time_workspace_bytes(int N, int S_max, int64_t B,
+                                             const mtg_time_params* params, int optimize);
+int mtg_ragged_tube_time_cost(mtg_ctx* ctx, int N, int r, int S_max, int64_t B,
+                              const int32_t* seg_counts, const double* positions,
+                              const double* fixed_vals, const double* times_cp,
+                              const double* times, const double* radii, double tol, int max_iter,
+                              const mtg_time_params* params, double* cost, double* grad,
+                              int32_t* status, void* workspace, size_t workspace_bytes,
+                              void* stream);
+int mtg_ragged_tube_time_optimize(mtg_ctx* ctx, int N, int r, int S_max, int64_t B,
+                                  const int32_t* seg_counts, const double* positions,
+                                  const double* fixed_vals, const double* radii,
+                                  double* times_io, double tol, int max_iter,
+                                  const mtg_time_params* params, int max_evals, double* cost,
+                                  int32_t* evals, int32_t* result, int32_t* status,
+                                  void* workspace, size_t workspace_bytes, void* stream);
+
 int64_t mtg_coll_workspace_bytes(const mtg_plan* plan, int64_t B, int mode,
                                  const mtg_coll_params* params, int optimize);
 /* near_field: mtg_coll_field of the same occupancy and box_side, or NULL

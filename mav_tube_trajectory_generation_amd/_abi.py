@@ -267,6 +267,21 @@ SIGNATURES = {
                                                  _vp, ctypes.c_double, ctypes.c_int,
                                                  ctypes.POINTER(TimeParams), ctypes.c_int, _vp,
                                                  _vp, _vp, _vp, _vp, ctypes.c_size_t, _vp]),
+    "mtg_ragged_tube_time_workspace_bytes": (ctypes.c_int64, [ctypes.c_int, ctypes.c_int,
+                                                              ctypes.c_int64,
+                                                              ctypes.POINTER(TimeParams),
+                                                              ctypes.c_int]),
+    "mtg_ragged_tube_time_cost": (ctypes.c_int, [_vp, ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                                                 ctypes.c_int64, _vp, _vp, _vp, _vp, _vp, _vp,
+                                                 ctypes.c_double, ctypes.c_int,
+                                                 ctypes.POINTER(TimeParams), _vp, _vp, _vp, _vp,
+                                                 ctypes.c_size_t, _vp]),
+    "mtg_ragged_tube_time_optimize": (ctypes.c_int, [_vp, ctypes.c_int, ctypes.c_int,
+                                                     ctypes.c_int, ctypes.c_int64, _vp, _vp, _vp,
+                                                     _vp, _vp, ctypes.c_double, ctypes.c_int,
+                                                     ctypes.POINTER(TimeParams), ctypes.c_int,
+                                                     _vp, _vp, _vp, _vp, _vp, ctypes.c_size_t,
+                                                     _vp]),
     "mtg_select_local": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64,
                                          ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p]),
     "mtg_select_workspace_bytes": (ctypes.c_int64, [_vp, ctypes.c_int64]),

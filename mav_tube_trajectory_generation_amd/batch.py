@@ -1116,6 +1116,78 @@ def tube_time_optimize(ctx, N, r, positions, fixed_vals, radii, times, max_evals
     return dict(times=t, cost=cost, evals=evals, result=result, status=status)
 
 
+def ragged_tube_time_workspace_bytes(N, S_max, B, params, optimize):
+    """Device scratch the ragged QCQP time objective / optimiser needs
+    (mtg_ragged_tube_time_workspace_bytes)."""
+    n = lib().mtg_ragged_tube_time_workspace_bytes(N, S_max, B, ctypes.byref(params),
+                                                   1 if optimize else 0)
+    if n < 0:
+        check(int(n), "mtg_ragged_tube_time_workspace_bytes")
+    return int(n)
+
+
+def ragged_tube_time_cost(ctx, N, r, seg_counts, positions, fixed_vals, times_cp, times, radii,
+                          time_penalty=500.0, grad=False, increment=0.1, soft=None,
+                          soft_weight=100.0, tol=1e-10, max_iter=100, workspace=None):
+    """tube_time_cost over a ragged batch in one call (mtg_ragged_tube_time_cost):
+    row b is the objective of its first S_b = seg_counts[b] segments.  Inputs
+    as pack_ragged_tube gives them (times_cp and times [B, S_max]; the padding
+    is never read); keywords as tube_time_cost.  Returns dict(cost [B], grad
+    [B, S_max] or None, status [B]); grad[b, S_b:] is 0.0.  A row whose count
+    is outside [2, S_max] has status 5, cost NaN and its grad row NaN.  The
+    counts stay on the device."""
+    import torch
+    B, S_max = _ragged_tube_inputs(N, seg_counts, positions, fixed_vals, times_cp, times, radii)
+    dev = times.device
+    p = make_time_params(time_penalty, increment, 0.1, 1.0, 2 if grad else 0, soft, soft_weight)
+    cost = torch.empty(B, dtype=torch.float64, device=dev)
+    g = torch.empty((B, S_max), dtype=torch.float64, device=dev) if grad else None
+    status = torch.empty(B, dtype=torch.int32, device=dev)
+    nbytes = ragged_tube_time_workspace_bytes(N, S_max, B, p, False)
+    ws = _workspace(workspace, nbytes, dev)
+    check(lib().mtg_ragged_tube_time_cost(
+        ctx.handle, N, r, S_max, B, _ptr(seg_counts), _ptr(positions), _ptr(fixed_vals),
+        _ptr(times_cp), _ptr(times), _ptr(radii), tol, max_iter, ctypes.byref(p), _ptr(cost),
+        _ptr(g), _ptr(status), _ptr(ws), ws.numel() * ws.element_size(), _stream(dev)),
+        "mtg_ragged_tube_time_cost")
+    return dict(cost=cost, grad=g, status=status)
+
+
+def ragged_tube_time_optimize(ctx, N, r, seg_counts, positions, fixed_vals, radii, times,
+                              max_evals, time_penalty=500.0, increment=0.1, soft=None,
+                              soft_weight=100.0, tol=1e-10, max_iter=100, workspace=None,
+                              optimizer="sbplx", f_rel=0.05, f_abs=-1.0,
+                              initial_stepsize_rel=0.1):
+    """tube_time_optimize(optimizer="sbplx") over a ragged batch in one call
+    (mtg_ragged_tube_time_optimize): row b runs LN_SBPLX over its first S_b
+    times.  times [B, S_max] are the initial times (and the control-point
+    times); inputs as pack_ragged_tube gives them, keywords as
+    tube_time_optimize.  Returns dict(times, cost, evals, result, status) with
+    new tensors; times[b, S_b:] keeps the input's bits.  A row whose count is
+    outside [2, S_max] has status 5, cost NaN, evals 0, result -1 and its
+    times unchanged.  optimizer="fd" is not available for ragged batches (the
+    call fails with MTG_ERR_UNSUPPORTED)."""
+    import torch
+    B, S_max = _ragged_tube_inputs(N, seg_counts, positions, fixed_vals, times, times, radii)
+    dev = times.device
+    p = make_time_params(time_penalty, increment, 0.1, 1.0, 2, soft, soft_weight,
+                         optimizer=optimizer, f_rel=f_rel, f_abs=f_abs,
+                         initial_stepsize_rel=initial_stepsize_rel)
+    nbytes = ragged_tube_time_workspace_bytes(N, S_max, B, p, True)
+    t = times.clone()
+    cost = torch.empty(B, dtype=torch.float64, device=dev)
+    evals = torch.empty(B, dtype=torch.int32, device=dev)
+    result = torch.empty(B, dtype=torch.int32, device=dev)
+    status = torch.empty(B, dtype=torch.int32, device=dev)
+    ws = _workspace(workspace, nbytes, dev)
+    check(lib().mtg_ragged_tube_time_optimize(
+        ctx.handle, N, r, S_max, B, _ptr(seg_counts), _ptr(positions), _ptr(fixed_vals),
+        _ptr(radii), _ptr(t), tol, max_iter, ctypes.byref(p), max_evals, _ptr(cost),
+        _ptr(evals), _ptr(result), _ptr(status), _ptr(ws), ws.numel() * ws.element_size(),
+        _stream(dev)), "mtg_ragged_tube_time_optimize")
+    return dict(times=t, cost=cost, evals=evals, result=result, status=status)
+
+
 def sample_trajectories(coeffs, times, dt, t_start=0.0, t_end=-1.0, max_derivative=0,
                         n_max=None, with_times=True):
     """Batched Trajectory::evaluateRange (trajectory.cpp:74-134) for derivatives

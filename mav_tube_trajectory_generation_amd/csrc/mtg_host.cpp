@@ -1327,6 +1327,84 @@ int mtg_tube_time_optimize(mtg_ctx* ctx, int N, int r, int S, int64_t B,
                                    workspace, workspace_bytes, stream);
 }
 
+// The ragged tube time entries: sizes, then what the kernels support, then the
+// parameters, then the problem grid, all before ctx or a pointer is looked at.
+static int ragged_tube_time_sizes(int N, int r, int S_max, int64_t B,
+                                  const mtg_time_params* params, bool optimize) {
+  if (!valid_N(N) || r < 0 || r > N / 2 - 1 || S_max < 2 || !tube_grid_ok(S_max, B))
+    return MTG_ERR_INVALID_ARG;
+  if (S_max > mtg::kMaxRaggedTubeTimeS ||
+      mtg::ragged_tube_lds_bytes(N, S_max) > static_cast<size_t>(mtg::kMaxLdsBytes))
+    return MTG_ERR_UNSUPPORTED;
+  if (!valid_tube_time_params(N, S_max, params)) return MTG_ERR_INVALID_ARG;
+  if (optimize) {
+    // optimizer 1: LN_SBPLX (the reference's default); 0, the projected
+    // descent, exists for uniform batches only
+    if (params->optimizer == 0) return MTG_ERR_UNSUPPORTED;
+    if (params->optimizer != 1) return MTG_ERR_INVALID_ARG;
+  } else {
+    if (params->grad_mode == 1) return MTG_ERR_UNSUPPORTED;
+    if (params->grad_mode != 0 && params->grad_mode != 2) return MTG_ERR_INVALID_ARG;
+  }
+  if (!tube_grid_ok(S_max, mtg::ragged_tube_time_problems(S_max, B, *params, optimize)))
+    return MTG_ERR_INVALID_ARG;
+  return MTG_OK;
+}
+
+int64_t mtg_ragged_tube_time_workspace_bytes(int N, int S_max, int64_t B,
+                                             const mtg_time_params* params, int optimize) {
+  const int rc = ragged_tube_time_sizes(N, N / 2 - 1, S_max, B, params, optimize != 0);
+  if (rc) return rc;
+  return static_cast<int64_t>(
+      mtg::ragged_tube_time_workspace_bytes(N, S_max, B, *params, optimize != 0));
+}
+
+int mtg_ragged_tube_time_cost(mtg_ctx* ctx, int N, int r, int S_max, int64_t B,
+                              const int32_t* seg_counts, const double* positions,
+                              const double* fixed_vals, const double* times_cp,
+                              const double* times, const double* radii, double tol, int max_iter,
+                              const mtg_time_params* params, double* cost, double* grad,
+                              int32_t* status, void* workspace, size_t workspace_bytes,
+                              void* stream) {
+  clear_stale_error();
+  int rc = ragged_tube_time_sizes(N, r, S_max, B, params, false);
+  if (rc) return rc;
+  if (!(tol > 0) || max_iter < 1) return MTG_ERR_INVALID_ARG;
+  mtg::RaggedTubeArgs a;
+  rc = ragged_tube_args(ctx, N, r, S_max, B, seg_counts, positions, fixed_vals, times_cp, times,
+                        radii, &a);
+  if (rc) return rc;
+  if (B && (!cost || (params->grad_mode == 2 && !grad))) return MTG_ERR_INVALID_ARG;
+  if (B == 0) return MTG_OK;
+  if (!workspace) return MTG_ERR_INVALID_ARG;
+  return mtg::ragged_tube_time_cost(a, tol, max_iter, *params, cost, grad, status, workspace,
+                                    workspace_bytes, static_cast<hipStream_t>(stream));
+}
+
+int mtg_ragged_tube_time_optimize(mtg_ctx* ctx, int N, int r, int S_max, int64_t B,
+                                  const int32_t* seg_counts, const double* positions,
+                                  const double* fixed_vals, const double* radii,
+                                  double* times_io, double tol, int max_iter,
+                                  const mtg_time_params* params, int max_evals, double* cost,
+                                  int32_t* evals, int32_t* result, int32_t* status,
+                                  void* workspace, size_t workspace_bytes, void* stream) {
+  clear_stale_error();
+  int rc = ragged_tube_time_sizes(N, r, S_max, B, params, true);
+  if (rc) return rc;
+  if (!(tol > 0) || max_iter < 1 || max_evals < 1) return MTG_ERR_INVALID_ARG;
+  mtg::RaggedTubeArgs a;
+  // times_cp = the initial times (copied to the workspace before the first
+  // write of times_io).
+  rc = ragged_tube_args(ctx, N, r, S_max, B, seg_counts, positions, fixed_vals, times_io,
+                        times_io, radii, &a);
+  if (rc) return rc;
+  if (B == 0) return MTG_OK;
+  if (!workspace) return MTG_ERR_INVALID_ARG;
+  return mtg::ragged_tube_time_optimize(a, times_io, tol, max_iter, *params, max_evals, cost,
+                                        evals, result, status, workspace, workspace_bytes,
+                                        static_cast<hipStream_t>(stream));
+}
+
 int mtg_generate_random_problems(int N, int D, int S, int64_t B, uint64_t seed0,
                                  double pos_bound, double v_max, double a_max,
                                  uint8_t* fixed_mask, double* fixed_vals, double* times,

@@ -248,6 +248,25 @@ hipError_t launch_ragged_tube_solve(const RaggedTubeArgs& a, double tol, int max
 // LDS per workgroup: the largest layout of the counts 2..S_max (capped just
 // above kMaxLdsBytes).
 size_t ragged_tube_lds_bytes(int N, int S_max);
+// Segment-time objective / LN_SBPLX optimiser with the QCQP inner solve over
+// a ragged batch (mtg_ragged_tube_time.hip): tube_time_cost and
+// tube_time_optimize (optimizer 1) per row with the row's own count; return
+// MTG_* codes.  a.times_cp / a.times are those of the cost entry; the
+// optimiser takes both from times_io.  S_max <= kMaxRaggedTubeTimeS: the rows
+// the ragged extrema kernel stages for the soft constraints.
+constexpr int kMaxRaggedTubeTimeS = kMaxStdS;
+size_t ragged_tube_time_workspace_bytes(int N, int S_max, int64_t B, const mtg_time_params& p,
+                                        bool optimiser);
+// QCQP problems of one launch (B x P_max evaluation points).
+int64_t ragged_tube_time_problems(int S_max, int64_t B, const mtg_time_params& p,
+                                  bool optimiser);
+int ragged_tube_time_cost(const RaggedTubeArgs& a, double tol, int max_iter,
+                          const mtg_time_params& p, double* cost, double* grad, int32_t* status,
+                          void* workspace, size_t workspace_bytes, hipStream_t st);
+int ragged_tube_time_optimize(const RaggedTubeArgs& a, double* times_io, double tol, int max_iter,
+                              const mtg_time_params& p, int max_evals, double* cost,
+                              int32_t* evals, int32_t* result, int32_t* status, void* workspace,
+                              size_t workspace_bytes, hipStream_t st);
 
 constexpr int kMaxLdsBytes = 160 * 1024;
 

@@ -22,6 +22,7 @@
 
 #include "mtg_internal.h"
 #include "mtg_sbplx_device.h"
+#include "mtg_tube_time_shared.h"
 
 namespace mtg {
 
@@ -249,41 +250,14 @@ __global__ void tube_time_opt_result_kernel(int64_t B, int max_evals, OptState s
   if (b < B) result[b] = s.evals[b] >= max_evals ? sbplx::kMaxEval : sbplx::kXtol;
 }
 
-// The next round's dispatch order (TubeArgs::order): a counting sort of the
-// trajectories by their last solve's IPM iterations, most first, the
-// finished ones last.  A solve's iteration count is the best predictor of
-// the next one's (consecutive points of a trajectory are close and share
-// their constraints), so dispatching longest-first keeps a round's few long
-// solves (up to the 100-iteration cap) from starting last and forming its
-// tail.  Ties are placed in any order: results do not depend on the order.
-constexpr int kOrderKeys = 128;
+// The next round's dispatch order (tube_time_order_body,
+// mtg_tube_time_shared.h).
 __global__ __launch_bounds__(1024) void tube_time_order_kernel(int64_t B,
                                                                const int32_t* __restrict__ iters,
                                                                const int32_t* __restrict__ done,
                                                                int32_t* __restrict__ order) {
-  __shared__ int cnt[kOrderKeys], off[kOrderKeys];
-  const int t = static_cast<int>(threadIdx.x);
-  for (int k = t; k < kOrderKeys; k += blockDim.x) cnt[k] = 0;
-  __syncthreads();
-  auto key = [&](int64_t b) {
-    const int it = iters[b];
-    return done[b] ? 0 : 1 + (it < 0 ? 0 : (it > kOrderKeys - 2 ? kOrderKeys - 2 : it));
-  };
-  for (int64_t b = t; b < B; b += blockDim.x) atomicAdd(&cnt[key(b)], 1);
-  __syncthreads();
-  if (t == 0) {
-    int run = 0;
-    for (int k = kOrderKeys - 1; k >= 0; --k) {
-      off[k] = run;
-      run += cnt[k];
-    }
-  }
-  __syncthreads();
-  for (int64_t b = t; b < B; b += blockDim.x)
-    order[atomicAdd(&off[key(b)], 1)] = static_cast<int32_t>(b);
+  tube_time_order_body(B, iters, done, order);
 }
-
-unsigned blocks_for(int64_t n) { return static_cast<unsigned>((n + 255) / 256); }
 
 // Caller-owned workspace (mtg_tube_time_workspace_bytes), carved in a fixed
 // order; each array starts on a 256-byte boundary.  With base == nullptr only
@@ -292,17 +266,6 @@ struct Workspace {
   double *coeffs, *pts, *qcost, *softc, *Jall, *maxima;
   int32_t* qstatus;
   OptState s;  // optimiser only
-};
-struct Carver {
-  char* base;
-  size_t off = 0;
-  template <typename T>
-  T* take(int64_t n) {
-    off = (off + 255) & ~size_t(255);
-    T* p = base ? reinterpret_cast<T*>(base + off) : nullptr;
-    off += sizeof(T) * static_cast<size_t>(n);
-    return p;
-  }
 };
 size_t carve(void* base, int N, int S, int64_t B, int P, int n_soft, bool optimiser,
              bool sbplx_opt, Workspace* w) {
