@@ -34,6 +34,19 @@ static_assert(kWpb >= 1 && kWpb <= 4, "1 to 4 waves per workgroup");
 #define MTG_WAVE_ENTRY32 1
 #endif
 
+// The cost phase's constants that no instruction carries (stdp::CostConsts),
+// in device memory: the kernel reads them with scalar loads at its entry.
+// Not const, so that the loads stay loads (a constant table folds back into
+// the instructions); nothing writes it.  A/B builds (5.1.1a):
+// -DMTG_WAVE_CONST_SGPR=0 leaves the constants to the compiler (s_mov_b32
+// pairs where they are used).
+#ifndef MTG_WAVE_CONST_SGPR
+#define MTG_WAVE_CONST_SGPR 1
+#endif
+#if MTG_WAVE_CONST_SGPR
+__device__ __attribute__((aligned(64))) stdp::CostConsts<10, 4> g_cost_consts{};
+#endif
+
 // The problem count nb is an argument in the first 64 bytes (the first 56
 // are preloaded into SGPRs; nb is the one scalar load before the first
 // global load, as gridDim.x was in round 4), and kPrev (this launch carries
@@ -101,6 +114,15 @@ __global__ __launch_bounds__(kWave * kWpb) void linear_wave_kernel(
     tr = tb[static_cast<unsigned>(sv.av)];
   }
   const double2 h_own = *reinterpret_cast<const double2*>(tab + 2 * (lane < N * N / 2 ? lane : 0));
+#if MTG_WAVE_CONST_SGPR
+  // The cost phase's constants, wave-uniform: scalar loads under the input
+  // loads' latency, held in SGPRs across the solve.
+  static_assert(N == 10 && R == 4, "g_cost_consts");
+  constexpr stdp::CostConsts<N, R> kC{};
+  double wc[kC.n];
+#pragma unroll
+  for (int i = 0; i < kC.n; ++i) wc[i] = g_cost_consts.v[i];
+#endif
   double* T = sv.aux();
 #if MTG_WAVE_ENTRY32
   // every lane stores (spare lanes to the junk area): no execution-mask
@@ -125,7 +147,9 @@ __global__ __launch_bounds__(kWave * kWpb) void linear_wave_kernel(
     if (status && lane == 0) status[b] = MTG_TRAJ_BAD_TIME;
     return;
   }
-  const bool not_spd = MTG_WAVE_T_DIRECT ? sv.solve(T, tl, tr) : sv.solve(T);
+  constexpr bool kPivInt = MTG_WAVE_PIVOT_INT;
+  const bool not_spd =
+      MTG_WAVE_T_DIRECT ? sv.template solve<kPivInt>(T, tl, tr) : sv.template solve<kPivInt>(T);
   // The coefficients are staged in the chain slots (free after solve()) and
   // copied out with consecutive lanes on consecutive 16-byte pieces: three
   // stores over 19 cache lines instead of five over 95 (lane (s, d) writes
@@ -133,7 +157,11 @@ __global__ __launch_bounds__(kWave * kWpb) void linear_wave_kernel(
   static_assert(2 * G::NSL * G::SLOT >= per, "coefficients fit the slots");
   double* stage = sv.slots;
 #ifndef MTG_ABL_NOCOEF  // diagnostic ablation builds only (tools/gpu_r05_abl.sh)
+#if MTG_WAVE_CONST_SGPR
+  const double J = sv.template coeff_cost<true>(T, stage, wc);
+#else
   const double J = sv.coeff_cost(T, stage);
+#endif
   lds_order();
   {
     copy_out16<kWave, per / 2>(reinterpret_cast<const double2*>(stage),

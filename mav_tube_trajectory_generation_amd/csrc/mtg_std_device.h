@@ -107,8 +107,9 @@ __device__ inline void ldlt_solve(const double (&S)[MF][MF], const double (&r)[M
 // operations) instead of LDL^T's four (about 28), which is what a sweep step
 // waits on at one wave per SIMD.  pmin as ldlt_solve: the leading minors
 // p00, det P, w00, det W' are all positive exactly when S is.
-__device__ inline void block2_solve(const double (&S)[4][4], const double (&r)[4],
-                                    double (&x)[4], double& pmin) {
+// The pivots go to piv; the two callers below fold them into their flag.
+__device__ inline void block2_solve_piv(const double (&S)[4][4], const double (&r)[4],
+                                        double (&x)[4], double (&piv)[4]) {
   const double p00 = S[0][0], p10 = S[1][0], p11 = S[1][1];
   const double detP = fma(p00, p11, -(p10 * p10));
   const double ip = rcp64_1(detP);
@@ -133,8 +134,58 @@ __device__ inline void block2_solve(const double (&S)[4][4], const double (&r)[4
   x[3] = fma(-w10, s0, w00 * s1) * iw;
   x[0] = fma(-Y01, x[3], fma(-Y00, x[2], y0));
   x[1] = fma(-Y11, x[3], fma(-Y10, x[2], y1));
-  pmin = fmin(pmin, fmin(fmin(p00, detP), fmin(w00, detW)));
+  piv[0] = p00;
+  piv[1] = detP;
+  piv[2] = w00;
+  piv[3] = detW;
 }
+__device__ inline void block2_solve(const double (&S)[4][4], const double (&r)[4],
+                                    double (&x)[4], double& pmin) {
+  double piv[4];
+  block2_solve_piv(S, r, x, piv);
+  pmin = fmin(pmin, fmin(fmin(piv[0], piv[1]), fmin(piv[2], piv[3])));
+}
+
+// The same flag for K block solves without FP64 issue slots.  The FP64 test
+// !(pmin > 0) flags a pivot that is <= 0 and not a NaN (fmin skips a NaN and
+// starts at 1.0).  hmin is the signed minimum of the pivots' high words, two
+// v_min3_i32 a solve.  hmin > 0: every pivot has its sign clear and a high
+// word that is not 0, so it is positive, +inf or a NaN: no flag.  Otherwise
+// (rare: a sign is set, or a high word is 0, which +0 and the subnormals
+// below 2^-1042 have) flagged() compares every kept pivot itself, p <= 0,
+// false for a NaN: the FP64 test's own answer.  Pivots of a solve that a lane
+// skips stay 1.0.
+template <int K>
+struct PivotWords {
+  double p[K][4];
+  int hmin;
+  __device__ void init() {
+    hmin = 0x3ff00000;
+#pragma unroll
+    for (int k = 0; k < K; ++k)
+#pragma unroll
+      for (int i = 0; i < 4; ++i) p[k][i] = 1.0;
+  }
+  static __device__ int high_word(double x) {
+    return static_cast<int>(__builtin_bit_cast(long long, x) >> 32);
+  }
+  __device__ void solve(int k, const double (&S)[4][4], const double (&r)[4], double (&x)[4]) {
+    block2_solve_piv(S, r, x, p[k]);
+    hmin = min(min(hmin, high_word(p[k][0])), high_word(p[k][1]));
+    hmin = min(min(hmin, high_word(p[k][2])), high_word(p[k][3]));
+  }
+  __device__ bool flagged() const {
+    int f = 0;  // (a count: an "or" of the tests folds back into an FP64 minimum)
+#pragma unroll
+    for (int k = 0; k < K; ++k) {
+#pragma unroll
+      for (int i = 0; i < 4; ++i) f += p[k][i] <= 0.0 ? 1 : 0;
+      // one solve's lane masks at a time (4 K SGPR pairs at once would spill)
+      __builtin_amdgcn_sched_barrier(0);
+    }
+    return f != 0;
+  }
+};
 
 template <int MF>
 __device__ inline void block_solve(const double (&S)[MF][MF], const double (&r)[MF],
@@ -244,6 +295,60 @@ struct CostW {
         v[i][j] = (i >= R && j >= R)
                       ? falling(R, i) * falling(R, j) / static_cast<double>(i + j - 2 * R + 1)
                       : 0.0;
+  }
+};
+
+// The constants of the coefficient and cost phase that a gfx950 FP64
+// instruction cannot carry itself.  Only v_fmac_f64 (VOP2) takes a literal,
+// and that is the high word of a double whose low word is 0; v_mul_f64 and
+// v_fma_f64 (VOP3) take none.  Every other constant costs an s_mov_b32 a
+// word where it is used.  Those are collected here, from the same tables:
+// entries with a low word, the factors of plain products (the diagonal of
+// A(1)^-1 in the rows i < M, the diagonal weights) and the first term of a
+// row i >= M (an fma onto 0).  ia / iw give an entry's index in v, or -1 for
+// one that stays a literal or an inline constant.  A kernel loads v with
+// scalar loads at its entry and hands the values to coeff_cost.
+template <int N, int R>
+struct CostConsts {
+  static constexpr int M = N / 2, kCap = 32;
+  double v[kCap];
+  int n;
+  signed char ia[N * N], iw[N][N];  // iw off the diagonal: of 2 w_ij
+  static constexpr bool inline_const(double x) {
+    const double a = x < 0.0 ? -x : x;
+    return a == 0.0 || a == 0.5 || a == 1.0 || a == 2.0 || a == 4.0;
+  }
+  static constexpr bool low_word(double x) {
+    return (__builtin_bit_cast(unsigned long long, x) & 0xffffffffull) != 0;
+  }
+  constexpr signed char slot(double x) {
+    for (int i = 0; i < n; ++i)
+      if (__builtin_bit_cast(unsigned long long, v[i]) == __builtin_bit_cast(unsigned long long, x))
+        return static_cast<signed char>(i);
+    v[n] = x;  // (past kCap: not a constant expression, a compile error)
+    return static_cast<signed char>(n++);
+  }
+  constexpr CostConsts() : v(), n(0), ia(), iw() {
+    const AInvTab<N> a{};
+    const CostW<N, R> w{};
+    for (int i = 0; i < N; ++i)
+      for (int j = 0; j < N; ++j) ia[i * N + j] = iw[i][j] = -1;
+    for (int i = 0; i < M; ++i)
+      if (!inline_const(a.v[i * N + i])) ia[i * N + i] = slot(a.v[i * N + i]);
+    for (int i = M; i < N; ++i) {
+      bool first = true;
+      for (int j = 0; j < N; ++j) {
+        const double x = a.v[i * N + j];
+        if (x == 0.0) continue;
+        if ((first && !inline_const(x)) || low_word(x)) ia[i * N + j] = slot(x);
+        first = false;
+      }
+    }
+    for (int i = R; i < N; ++i) {
+      if (!inline_const(w.v[i][i])) iw[i][i] = slot(w.v[i][i]);
+      for (int j = i + 1; j < N; ++j)
+        if (low_word(2.0 * w.v[i][j])) iw[i][j] = slot(2.0 * w.v[i][j]);
+    }
   }
 };
 
@@ -707,15 +812,24 @@ struct Solver {
     return q_form(h) * ps[1 - 2 * R];
   }
 
-  // sum_ij w_ij h_i h_j over i, j >= r.
-  __device__ static double q_form(const double (&h)[N]) {
+  // sum_ij w_ij h_i h_j over i, j >= r.  kTab: the weights CostConsts lists
+  // come from wc (its v, loaded by the caller), the same values.
+  template <bool kTab = false>
+  __device__ static double q_form(const double (&h)[N], const double* wc = nullptr) {
     constexpr CostW<N, R> kW{};
+    auto W = [&](int i, int j) {
+      if constexpr (kTab) {
+        constexpr CostConsts<N, R> kC{};
+        if (kC.iw[i][j] >= 0) return wc[kC.iw[i][j]];
+      }
+      return i == j ? kW.v[i][i] : 2.0 * kW.v[i][j];
+    };
     double q2 = 0.0;
 #pragma unroll
     for (int i = R; i < N; ++i) {
-      double t = kW.v[i][i] * h[i];
+      double t = W(i, i) * h[i];
 #pragma unroll
-      for (int j = i + 1; j < N; ++j) t = fma(2.0 * kW.v[i][j], h[j], t);
+      for (int j = i + 1; j < N; ++j) t = fma(W(i, j), h[j], t);
       q2 = fma(t, h[i], q2);
     }
     return q2;

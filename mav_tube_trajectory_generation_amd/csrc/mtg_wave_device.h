@@ -40,6 +40,11 @@
 #ifndef MTG_WAVE_MID_REG
 #define MTG_WAVE_MID_REG 1
 #endif
+// A/B build of the pivot flag (5.1.1a): -DMTG_WAVE_PIVOT_INT=0 keeps the C2
+// kernel on the FP64 minimum, as the time kernels are.
+#ifndef MTG_WAVE_PIVOT_INT
+#define MTG_WAVE_PIVOT_INT 1
+#endif
 
 namespace mtg {
 namespace wave {
@@ -252,7 +257,11 @@ struct Solver {
   // A solve at the segment times T (LDS, S valid values): dv receives every
   // vertex derivative.  Returns true if a pivot was not positive
   // (wave-uniform).  All lanes call.
-  __device__ bool solve(const double* T) { return solve(T, T[tl_index()], T[av]); }
+  // kPivInt: the flag from the pivots' high words (stdp::PivotWords).
+  template <bool kPivInt = false>
+  __device__ bool solve(const double* T) {
+    return solve<kPivInt>(T, T[tl_index()], T[av]);
+  }
   // The segment whose time is the assembly lane's left time: segment av - 1
   // for a row lane, the end segment for an end lane of the same pass.
   __device__ int tl_index() const {
@@ -260,6 +269,7 @@ struct Solver {
   }
   // The same with the lane's times T[tl_index()] and T[av] given (a caller
   // that has them from memory spares the assembly the LDS hop).
+  template <bool kPivInt = false>
   __device__ bool solve(const double* T, double tl, double tr) {
     // With no backward step (S = 2) the middle vertex reads the backward
     // chain's terminal slot as zero; otherwise its last step writes it.
@@ -385,6 +395,8 @@ struct Solver {
     // r[d]), out_i = a_i - P[:, i] . x into slot k+1 (the next Schur block or
     // right-hand side), x_i into slot k (Z[i][j], or z[d][i] in place of r).
     double pmin = 1.0;
+    [[maybe_unused]] stdp::PivotWords<kPivInt ? NK + 1 : 1> pw;
+    if constexpr (kPivInt) pw.init();
     {
       // lanes past the MF + D columns repeat column 0 (same values, same
       // addresses), so the sweep needs no execution mask
@@ -437,7 +449,10 @@ struct Solver {
               lds_ld(Pp + (k + 1) * SLOT, pcn);
               an = Ap[(k + 1) * SLOT];
             }
-            block2_solve(Sv, u, x, pmin);
+            if constexpr (kPivInt)
+              pw.solve(k, Sv, u, x);
+            else
+              block2_solve(Sv, u, x, pmin);
             // The backward chain's last step forms 0 - P^T x (the backward
             // terms of the middle vertex): a is 0 there.
             if (k == NBW - 1) a = g ? 0.0 : a;
@@ -523,7 +538,10 @@ struct Solver {
         zz[t] = zb[sidx * SLOT];
         lds_ld(Zb + sidx * SLOT, zr[t]);
       }
-      block2_solve(Sv, rr, x, pmin);
+      if constexpr (kPivInt)
+        pw.solve(NK, Sv, rr, x);
+      else
+        block2_solve(Sv, rr, x, pmin);
       double xi = i1 ? x[1] : x[0];
       xi = i2 ? x[2] : xi;
       xi = i3 ? x[3] : xi;
@@ -543,7 +561,13 @@ struct Solver {
         }
       }
     }
-    const bool not_spd = __any(!(pmin > 0.0));
+    bool not_spd;
+    if constexpr (kPivInt) {
+      not_spd = false;
+      if (__builtin_expect(__any(pw.hmin <= 0), 0)) not_spd = __any(pw.flagged());
+    } else {
+      not_spd = __any(!(pmin > 0.0));
+    }
     lds_order();
     MTG_STAMP(5);
     return not_spd;
@@ -553,11 +577,20 @@ struct Solver {
   // coefficients (S x D x N) go to out (global or LDS, 16-byte aligned) when
   // out != nullptr.  Lane (s, d): f_j = e_j T^(j mod M), h = A(1)^-1 f,
   // c_i = T^-i h_i, 0.5 c^T Q c = T^(1-2r) sum w_ij h_i h_j (A(1)^-1 and w
-  // are instruction literals).
-  __device__ double coeff_cost(const double* T, double* out) const {
+  // are instruction literals; kTab: those stdp::CostConsts lists come from
+  // wc, its v loaded by the caller, wave-uniform).
+  template <bool kTab = false>
+  __device__ double coeff_cost(const double* T, double* out, const double* wc = nullptr) const {
     double acc = 0.0;
     if (lane < S * D) {
       constexpr AInvTab<N> kA{};
+      auto A = [&](int i, int j) {
+        if constexpr (kTab) {
+          constexpr stdp::CostConsts<N, R> kC{};
+          if (kC.ia[i * N + j] >= 0) return wc[kC.ia[i * N + j]];
+        }
+        return kA.v[i * N + j];
+      };
       const double ts = T[cs];
       double e[N], f[N], h[N];
       {
@@ -581,13 +614,13 @@ struct Solver {
 #pragma unroll
       for (int j = 0; j < N; ++j) f[j] = e[j] * tp[j % M];
 #pragma unroll
-      for (int i = 0; i < M; ++i) h[i] = kA.v[i * N + i] * f[i];
+      for (int i = 0; i < M; ++i) h[i] = A(i, i) * f[i];
 #pragma unroll
       for (int i = M; i < N; ++i) {
         double t = 0.0;
 #pragma unroll
         for (int j = 0; j < N; ++j)
-          if (kA.v[i * N + j] != 0.0) t = fma(kA.v[i * N + j], f[j], t);
+          if (kA.v[i * N + j] != 0.0) t = fma(A(i, j), f[j], t);
         h[i] = t;
       }
       if (out) {
@@ -598,7 +631,7 @@ struct Solver {
 #pragma unroll
         for (int i = 0; i < N / 2; ++i) o2[i] = make_double2(cc[2 * i], cc[2 * i + 1]);
       }
-      acc = stdp::Solver<N, R, D>::q_form(h) * ipow<1 - 2 * R>(ts, inv);
+      acc = stdp::Solver<N, R, D>::template q_form<kTab>(h, wc) * ipow<1 - 2 * R>(ts, inv);
     }
     return wave_sum_dpp(acc);
   }
