@@ -5,6 +5,13 @@ absent: parity of the solve is against the oracle's own interior-point method
 ("parity unpinned" vs MOSEK; the oracle IPM is cross-checked with SciPy in
 tests/test_tube_oracle.py).  Constraint residuals are pinned to the oracle's
 reference-faithful assembly of qcqp_impl:321-474.
+
+The oracle's IPM is the kernel's own algorithm, and rows it does not converge
+on are skipped below.  tests/test_tube_dual_gpu.py holds the same kernels to
+a reference that depends on no solver: a weak-duality lower bound on the cost
+from stored multipliers (tests/tube_cert.py, tests/golden/tube_dual.json), at
+every order, every compile-time S named here, S = 17, the time box's edge
+with stale control-point maps, ragged rows and the J of the time objectives.
 """
 import numpy as np
 import pytest
