@@ -27,19 +27,6 @@ namespace mtg {
 
 namespace {
 
-// The launch shape of tube_solve_kernel<N> (mtg_tube.hip).
-template <int N>
-constexpr int ragged_tube_threads() { return N <= 10 ? 2 * kWave : kWave; }
-
-template <int N>
-__device__ inline Tube<N> make_ragged_tube(const TubeLayout* L, double* smem, int S, int r,
-                                           const double* tab) {
-  const int tid = static_cast<int>(threadIdx.x);
-  return Tube<N>{S,   r,         S - 1, tube_ncon(N, S), L, smem, tid & (kWave - 1), tab,
-                 tid, static_cast<int>(blockDim.x),
-                 __builtin_amdgcn_readfirstlane(tid / kWave)};
-}
-
 // The inputs of row b, each at its padded stride.
 struct RaggedTubeRow {
   const double *positions, *fixed_vals, *times_cp, *times, *radii;
@@ -77,7 +64,7 @@ __global__ __launch_bounds__(kWave) void ragged_tube_residuals_kernel(
     return;
   }
   const TubeLayout L = make_tube_layout(N, S);
-  Tube<N> t = make_ragged_tube<N>(&L, smem, S, r, tab);
+  Tube<N> t = make_tube<N>(&L, smem, S, r, tab);
   int* bad = reinterpret_cast<int*>(smem + L.ndouble);
   const RaggedTubeRow in =
       ragged_tube_row(b, N, S_max, positions, fixed_vals, times_cp, times, radii);
@@ -104,12 +91,12 @@ __global__ __launch_bounds__(kWave) void ragged_tube_residuals_kernel(
   }
 }
 
-// tube_solve_body (mtg_tube.hip) per row with the row's own S, without the
-// warm start, the skip flags and the evaluation points.
+// tube_solve_one (mtg_tube_device.h) per row with the row's own S, without
+// the warm start.
 template <int N>
-__global__ __launch_bounds__(ragged_tube_threads<N>())
-__attribute__((amdgpu_waves_per_eu(ragged_tube_threads<N>() / kWave,
-                                   ragged_tube_threads<N>() / kWave)))
+__global__ __launch_bounds__(tube_threads<N>())
+__attribute__((amdgpu_waves_per_eu(tube_threads<N>() / kWave,
+                                   tube_threads<N>() / kWave)))
 void ragged_tube_solve_kernel(
     int S_max, int r, const int32_t* __restrict__ seg_counts, const double* __restrict__ tab,
     const double* __restrict__ positions, const double* __restrict__ fixed_vals,
@@ -117,87 +104,22 @@ void ragged_tube_solve_kernel(
     const double* __restrict__ radii, double tol, int max_iter, double* __restrict__ x_out,
     double* __restrict__ coeffs, double* __restrict__ cost, int32_t* __restrict__ iters,
     int32_t* __restrict__ status, const int32_t* __restrict__ order) {
-  extern __shared__ __attribute__((aligned(16))) double smem[];
   constexpr int M = N / 2;
   // The row of this workgroup: order[blockIdx.x] (the longest rows first:
   // ragged_tube_order_kernel), else the XCD-contiguous map (mtg_device.h).
   const int64_t b = order ? order[blockIdx.x] : xcd_problem(blockIdx.x, gridDim.x);
-  const int tid = static_cast<int>(threadIdx.x);
-  const int nthr = static_cast<int>(blockDim.x);
-  // One path to the end for every row, as in tube_solve_body: with a return
-  // ahead of the IPM the N = 10 kernel spills 76 B per lane, without 64 B
-  // (tube_solve_kernel<10>: 72 B).  A row that is not a
-  // trajectory is therefore set up as two segments (inside its own padded
-  // row and the launch's LDS, S_max >= 2; the values are never used), skips
-  // the IPM like a row with a bad time, and its outputs are NaN.
+  // A row that is not a trajectory goes through the body as two segments
+  // (inside its own padded row and the launch's LDS, S_max >= 2; the values
+  // are never used) instead of returning here: see tube_solve_one.
   const int Sr = __builtin_amdgcn_readfirstlane(seg_counts[b]);
   const bool valid = Sr >= 2 && Sr <= S_max;
-  const int S = valid ? Sr : 2;
-  const int row_max = (S_max - 1) * M;
-  const int per_max = S_max * 3 * N;
-  double* xb = x_out ? x_out + b * 3 * row_max : nullptr;
-  double* cb = coeffs + b * per_max;
-  const TubeLayout L = make_tube_layout(N, S);
-  Tube<N> t = make_ragged_tube<N>(&L, smem, S, r, tab);
-  int* bad = reinterpret_cast<int*>(smem + L.ndouble);
   const RaggedTubeRow in =
       ragged_tube_row(b, N, S_max, positions, fixed_vals, times_cp, times, radii);
-  t.setup(tab, 0, 0, in.positions, in.fixed_vals, in.times_cp, in.times, in.radii, bad);
-  int st = 1;
-  int it = 0;
-  if (valid && !(*bad & 1)) it = t.ipm(tol, max_iter, &st, bad, nullptr);
-  __syncthreads();
-  // Bit 0: a time is not positive; a row that is not a trajectory counts
-  // likewise: NaN over the whole padded row.  Bit 1: the start system is not
-  // positive definite, so x was never written: NaN over the row's values.
-  const int fl = *bad;
-  const bool dead = !valid || (fl & 1) != 0;
-  const bool no_x = dead || (fl & 2) != 0;
-  // The powers share LDS with the factors: recompute them for the outputs.
-  if (!dead) t.compute_powers();
-  __syncthreads();
-  const int row = (S - 1) * M;
-  if (xb)
-    for (int idx = tid; idx < 3 * row_max; idx += nthr) {
-      const int d = idx / row_max, j = idx % row_max;
-      double v = dead ? NAN : 0.0;
-      if (j < row) {
-        const int a = j / M, m = j % M;
-        v = smem[L.x + (a * 3 + d) * M + m];
-        v = no_x ? NAN : (m == 0 ? v + tube_origin(in.positions, 0, S, d) : v);
-      }
-      xb[idx] = v;
-    }
-  const double* xv = smem + L.x;
-  double acc = 0.0;
-  const int per = S * 3 * N;
-  for (int i = tid; i < per; i += nthr) {
-    const int s = i / (3 * N), d = (i / N) % 3, k = i % N;
-    const int lk = k % M;
-    double c = 0.0, h = 0.0;
-#pragma unroll
-    for (int j = 0; j < N; ++j) {
-      const int l = j % M;
-      const double e = t.xval(xv, s + j / M, d, l);
-      c += tab[N * N + k * N + j] * t.pwr(s, l - k) * e;
-      h += tab[k * N + j] * t.pwr(s, 1 - 2 * r + lk + l) * e;
-    }
-    cb[i] = no_x ? NAN : (k == 0 ? c + tube_origin(in.positions, 0, S, d) : c);
-    acc += h * t.xval(xv, s + k / M, d, lk);
-  }
-  for (int i = per + tid; i < per_max; i += nthr) cb[i] = dead ? NAN : 0.0;
-  const double J = 0.5 * t.block_sum(acc);
-  if (tid == 0) {
-    if (cost) cost[b] = no_x ? NAN : J;
-    if (iters) iters[b] = dead ? 0 : it;
-    if (status)
-      status[b] = !valid              ? MTG_TRAJ_BAD_SEGMENTS
-                  : (fl & 1)          ? MTG_TRAJ_BAD_TIME
-                  : (no_x || st == 2) ? MTG_TRAJ_NOT_SPD
-                  : st == 0           ? MTG_TRAJ_OK
-                  : st == 3           ? MTG_TRAJ_NEAR_OPTIMAL
-                                      : MTG_TRAJ_NOT_CONVERGED;
-  }
+  tube_solve_one<N>(valid ? Sr : 2, S_max, valid, r, tab, in.positions, in.fixed_vals,
+                    in.times_cp, in.times, in.radii, tol, max_iter,
+                    x_out ? x_out + b * 3 * (S_max - 1) * M : nullptr,
+                    coeffs + b * S_max * 3 * N, b, cost, iters, status, nullptr, nullptr,
+                    &Tube<N>::ipm);
 }
 
 // The dispatch order of ragged_tube_solve_kernel: a counting sort of the rows
@@ -265,7 +187,7 @@ hipError_t launch_ragged_tube_solve(const RaggedTubeArgs& a, double tol, int max
     if (e != hipSuccess) return e;
   }
   return with_order(a.N, [&](auto n) {
-    return launch(ragged_tube_solve_kernel<n()>, a.B, ragged_tube_threads<n()>(),
+    return launch(ragged_tube_solve_kernel<n()>, a.B, tube_threads<n()>(),
                   ragged_tube_lds_bytes(a.N, a.S_max), st, a.S_max, a.r, a.seg_counts, a.tab,
                   a.positions, a.fixed_vals, a.times_cp, a.times, a.radii, tol, max_iter, x,
                   coeffs, cost, iters, status, static_cast<const int32_t*>(order_ws));

@@ -36,10 +36,6 @@ namespace {
 
 constexpr double kLower = 0.1;  // kOptimizationTimeLowerBound (nonlinear_impl:370)
 
-// The launch shape of ragged_tube_solve_kernel<N> (mtg_ragged_tube.hip).
-template <int N>
-constexpr int ragged_eval_threads() { return N <= 10 ? 2 * kWave : kWave; }
-
 __device__ inline bool count_ok(int S, int S_max) { return S >= 2 && S <= S_max; }
 
 // Row j of the evaluation points of trajectory b from its times T (stride
@@ -120,10 +116,6 @@ struct OptState {
   int32_t* order;  // the next round's dispatch order
 };
 
-__device__ inline sbplx::State* sb_state(const OptState& s, int64_t b) {
-  return reinterpret_cast<sbplx::State*>(s.sb + static_cast<size_t>(b) * s.sb_bytes);
-}
-
 // tube_time_sbplx_init_kernel with n = S_b.  A row whose count is out of
 // range never starts: it is done from the outset and the final kernel writes
 // its failure values.
@@ -153,16 +145,13 @@ __global__ void ragged_tube_time_sbplx_init_kernel(int S_max, int64_t B,
   s.st[b] = MTG_TRAJ_OK;
 }
 
+// The machine's step between rounds (tube_time_sbplx_step_body,
+// mtg_tube_time_shared.h).
 __global__ void ragged_tube_time_sbplx_step_kernel(int S_max, int64_t B, int first,
                                                    const double* __restrict__ Jall,
                                                    const int32_t* __restrict__ qstatus,
                                                    OptState s) {
-  const int64_t b = static_cast<int64_t>(blockIdx.x) * blockDim.x + threadIdx.x;
-  if (b >= B || s.done[b]) return;
-  if (first) s.st[b] = qstatus[b];
-  sbplx::Machine m{sb_state(s, b)};
-  m.resume(Jall[b], s.Ttr + b * S_max);
-  if (m.s->done) s.done[b] = 1;
+  tube_time_sbplx_step_body(S_max, B, first, Jall, qstatus, s);
 }
 
 // tube_time_sbplx_final_kernel: the first S_b entries of times_io only.  A
@@ -204,19 +193,20 @@ __global__ __launch_bounds__(1024) void ragged_tube_time_order_kernel(
 
 }  // namespace
 
-// One QCQP per live problem: ragged_tube_solve_kernel (mtg_ragged_tube.hip)
-// with what tube_solve_body (mtg_tube.hip) has and the ragged solve lacks.
+// One QCQP per live problem: tube_solve_one (mtg_tube_device.h) with padded
+// rows, the warm start and no x output.
 // Problem q = b P + j takes its geometry and T0 maps from trajectory b = q / P
 // at the padded strides, its times from row q of the points buffer, and its
 // count from pcount[q]: S_b where the problem is live, 0 where it is to be
 // skipped (the workgroup then returns without touching any output).  The
 // warm-start state of problem q starts at q tube_warm_doubles(N, S_max) and is
 // carved for S_b.  coeffs is the layout the ragged extrema kernel reads:
-// segments >= S_b are written 0.0.
+// segments >= S_b are written 0.0, or NaN like the rest of the row where the
+// problem has a bad time (the extrema kernel reads the first S_b only).
 template <int N>
-__global__ __launch_bounds__(ragged_eval_threads<N>())
-__attribute__((amdgpu_waves_per_eu(ragged_eval_threads<N>() / kWave,
-                                   ragged_eval_threads<N>() / kWave)))
+__global__ __launch_bounds__(tube_threads<N>())
+__attribute__((amdgpu_waves_per_eu(tube_threads<N>() / kWave,
+                                   tube_threads<N>() / kWave)))
 void ragged_tube_eval_kernel(
     int S_max, int r, int P, const int32_t* __restrict__ pcount, const double* __restrict__ tab,
     const double* __restrict__ positions, const double* __restrict__ fixed_vals,
@@ -225,7 +215,6 @@ void ragged_tube_eval_kernel(
     double* __restrict__ qcost, int32_t* __restrict__ iters, int32_t* __restrict__ qstatus,
     double* __restrict__ warm, int32_t* __restrict__ warm_ok,
     const int32_t* __restrict__ order) {
-  extern __shared__ __attribute__((aligned(16))) double smem[];
   constexpr int M = N / 2;
   const int64_t q = order ? order[blockIdx.x] : xcd_problem(blockIdx.x, gridDim.x);
   // Workgroup-uniform.  Anything but a count the launch's LDS and the padded
@@ -233,72 +222,13 @@ void ragged_tube_eval_kernel(
   const int S = __builtin_amdgcn_readfirstlane(pcount[q]);
   if (!count_ok(S, S_max)) return;
   const int64_t b = q / P;
-  const int tid = static_cast<int>(threadIdx.x);
-  const int nthr = static_cast<int>(blockDim.x);
-  const double* pos = positions + b * (S_max + 1) * 3;
-  const TubeLayout L = make_tube_layout(N, S);
-  Tube<N> t{S,   r,    S - 1, tube_ncon(N, S), &L, smem, tid & (kWave - 1), tab,
-            tid, nthr, __builtin_amdgcn_readfirstlane(tid / kWave)};
-  int* bad = reinterpret_cast<int*>(smem + L.ndouble);
-  // One vertex (S_b = 2) has no coupling block: the layout still holds one
-  // M x M slot for it, Tube::setup writes none of it, and Tube::factor loads
-  // it with a clamped index and multiplies it by a role factor of 0.0.  What
-  // an earlier workgroup left there enters as 0.0 x word: NaN where the word
-  // is NaN or inf, and then the pivot, the factorisation and the row's result
-  // depend on what ran on the CU before.  Written here (workgroup-uniform;
-  // setup's barriers order it ahead of every factor()).
-  if (S == 2)
-    for (int i = tid; i < M * M; i += nthr) smem[L.Po + i] = 0.0;
-  t.setup(tab, 0, 0, pos, fixed_vals + b * 3 * N, times_cp + b * S_max, pts + q * S_max,
-          radii + b * S_max * 2, bad);
-  int st = 1;
-  int it = 0;
-  double* ws = warm ? warm + q * (static_cast<int64_t>(S_max - 1) * 3 * M +
-                                  2 * tube_ncon(N, S_max))
-                    : nullptr;
-  const bool use_ws = warm && warm_ok[q];
-  if (!(*bad & 1)) it = t.ipm(tol, max_iter, &st, bad, use_ws ? ws : nullptr);
-  __syncthreads();
-  if (warm && !(*bad & 3) && st != 2) {
-    t.save_state(ws);
-    if (tid == 0) warm_ok[q] = 1;
-  }
-  // Bit 0: a time is not positive; bit 1: the start system is not positive
-  // definite, so x was never written.  Either way the outputs are NaN.
-  const int fl = *bad;
-  const bool no_x = (fl & 3) != 0;
-  // The powers share LDS with the factors: recompute them for the outputs.
-  if (!(fl & 1)) t.compute_powers();
-  __syncthreads();
-  const double* xv = smem + L.x;
-  double acc = 0.0;
-  const int per = S * 3 * N, per_max = S_max * 3 * N;
-  double* cb = coeffs + q * per_max;
-  for (int i = tid; i < per; i += nthr) {
-    const int s = i / (3 * N), d = (i / N) % 3, k = i % N;
-    const int lk = k % M;
-    double c = 0.0, h = 0.0;
-#pragma unroll
-    for (int j = 0; j < N; ++j) {
-      const int l = j % M;
-      const double e = t.xval(xv, s + j / M, d, l);
-      c += tab[N * N + k * N + j] * t.pwr(s, l - k) * e;
-      h += tab[k * N + j] * t.pwr(s, 1 - 2 * r + lk + l) * e;
-    }
-    cb[i] = no_x ? NAN : (k == 0 ? c + tube_origin(pos, 0, S, d) : c);
-    acc += h * t.xval(xv, s + k / M, d, lk);
-  }
-  for (int i = per + tid; i < per_max; i += nthr) cb[i] = 0.0;
-  const double J = 0.5 * t.block_sum(acc);
-  if (tid == 0) {
-    qcost[q] = no_x ? NAN : J;
-    if (iters) iters[q] = it;
-    qstatus[q] = (fl & 1)                ? MTG_TRAJ_BAD_TIME
-                 : ((fl & 2) || st == 2) ? MTG_TRAJ_NOT_SPD
-                 : st == 0               ? MTG_TRAJ_OK
-                 : st == 3               ? MTG_TRAJ_NEAR_OPTIMAL
-                                         : MTG_TRAJ_NOT_CONVERGED;
-  }
+  tube_solve_one<N>(
+      S, S_max, true, r, tab, positions + b * (S_max + 1) * 3, fixed_vals + b * 3 * N,
+      times_cp + b * S_max, pts + q * S_max, radii + b * S_max * 2, tol, max_iter, nullptr,
+      coeffs + q * S_max * 3 * N, q, qcost, iters, qstatus,
+      warm ? warm + q * (static_cast<int64_t>(S_max - 1) * 3 * M + 2 * tube_ncon(N, S_max))
+           : nullptr,
+      warm_ok, &Tube<N>::ipm);
 }
 
 namespace {
@@ -369,7 +299,7 @@ hipError_t evaluate_points(const RaggedTubeArgs& a, int P, const Round& rd, doub
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) return e;
   e = with_order(a.N, [&](auto n) {
-    return launch(ragged_tube_eval_kernel<n()>, BP, ragged_eval_threads<n()>(),
+    return launch(ragged_tube_eval_kernel<n()>, BP, tube_threads<n()>(),
                   ragged_tube_lds_bytes(a.N, S_max), st, S_max, a.r, P,
                   static_cast<const int32_t*>(w.pcount), a.tab, a.positions, a.fixed_vals,
                   a.times_cp, static_cast<const double*>(w.pts), a.radii, tol, max_iter,

@@ -10,15 +10,6 @@
 
 namespace mtg {
 
-template <int N>
-__device__ inline Tube<N> make_tube(const TubeLayout* L, double* smem, int S, int r,
-                                    const double* tab) {
-  const int tid = static_cast<int>(threadIdx.x);
-  return Tube<N>{S,   r,         S - 1, tube_ncon(N, S), L, smem, tid & (kWave - 1), tab,
-                 tid, static_cast<int>(blockDim.x),
-                 __builtin_amdgcn_readfirstlane(tid / kWave)};
-}
-
 // Constraint residuals g_k(x) (compute_sphere/tube/tube_end_constraints,
 // qcqp_impl:357-474) at x given in the reference's dimension-major order.
 template <int N>
@@ -51,16 +42,13 @@ __global__ __launch_bounds__(kWave) void tube_residuals_kernel(
   }
 }
 
-// Two waves per trajectory for N <= 10: both run the data-parallel phases,
-// wave 0 the block factorisation and solves; with 40 KB of LDS per
-// trajectory a CU holds 4 trajectories = 8 waves, two per SIMD (registers
-// capped at 256 per wave).  N = 12 keeps one wave (its 18 x 18 blocks need
-// more registers than two waves per SIMD leave).
-template <int N>
-constexpr int tube_threads() { return N <= 10 ? 2 * kWave : kWave; }
-
 // The kernel body for S segments (a kernel argument, or a compile-time
-// constant in tube_solve_s_kernel).
+// constant in tube_solve_s_kernel).  The ragged kernels share one body,
+// tube_solve_one (mtg_tube_device.h), which is this one with padded output
+// rows; the uniform kernels keep their own copy because through the shared
+// body tube_solve_s_kernel<10, 10> measured 0.2 % slower on the time-qcqp
+// workload (profiles/tube_one_body_ab.txt).  A change to the
+// output phase or the IPM hand-off is made here and there.
 template <int N>
 __device__ __attribute__((always_inline)) void tube_solve_body(
     int S, int r, int rep, const double* __restrict__ tab, const double* __restrict__ positions,
@@ -80,6 +68,9 @@ __device__ __attribute__((always_inline)) void tube_solve_body(
   Tube<N> t = make_tube<N>(&L, smem, S, r, tab);
   int* bad = reinterpret_cast<int*>(smem + L.ndouble);
   constexpr int M = N / 2;
+  // The coupling slot nobody writes for one vertex (see tube_solve_one).
+  if (S == 2)
+    for (int i = t.tid; i < M * M; i += t.nthr) smem[L.Po + i] = 0.0;
   t.setup(tab, b, b / rep, positions, fixed_vals, times_cp, times, radii, bad);
   int st = 1;
   int it = 0;

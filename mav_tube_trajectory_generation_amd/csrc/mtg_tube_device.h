@@ -1239,4 +1239,146 @@ struct Tube {
   }
 };
 
+// Two waves per trajectory for N <= 10: both run the data-parallel phases,
+// wave 0 the block factorisation and solves; with 40 KB of LDS per
+// trajectory a CU holds 4 trajectories = 8 waves, two per SIMD (registers
+// capped at 256 per wave).  N = 12 keeps one wave (its 18 x 18 blocks need
+// more registers than two waves per SIMD leave).  The launch shape of every
+// solve kernel, of uniform and of ragged batches.
+template <int N>
+constexpr int tube_threads() { return N <= 10 ? 2 * kWave : kWave; }
+
+// The workgroup's Tube<N> for S segments in the layout L carved from smem.
+template <int N>
+__device__ inline Tube<N> make_tube(const TubeLayout* L, double* smem, int S, int r,
+                                    const double* tab) {
+  const int tid = static_cast<int>(threadIdx.x);
+  return Tube<N>{S,   r,         S - 1, tube_ncon(N, S), L, smem, tid & (kWave - 1), tab,
+                 tid, static_cast<int>(blockDim.x),
+                 __builtin_amdgcn_readfirstlane(tid / kWave)};
+}
+
+// Tube<N>::ipm as tube_solve_one's callers hand it over.
+template <int N>
+using TubeIpm = int (Tube<N>::*)(double, int, int*, int*, const double*);
+
+// Solves one tube problem in this workgroup: the body of the solve kernels of
+// ragged batches (ragged_tube_solve_kernel, mtg_ragged_tube.hip;
+// ragged_tube_eval_kernel, mtg_ragged_tube_time.hip).  It is tube_solve_body
+// (mtg_tube.hip, the uniform kernels' own copy: see there) with padded output
+// rows.  The problem has S segments (workgroup-uniform, 2 <= S <= S_pad) and
+// its outputs are rows padded for S_pad segments.  The rows are the problem's
+// own:
+//   positions (S+1) x 3, fixed_vals 3 x N, times_cp S, times S, radii S x 2
+//   x       3 x (S_pad-1)M  row d: (S-1)M values, then the pad     (nullable)
+//   coeffs  S_pad x 3 x N   segments >= S are pad
+//   ws      the warm-start state: x, s, lam in the layouts of S    (nullable)
+// and the one-word outputs are the launch's arrays, written at the problem's
+// index q (cost, iters, status: nullable; warm_ok: read and written where ws).
+// !valid marks a row that is not a trajectory (the caller passes S = 2, whose
+// inputs lie inside any padded row): it skips the IPM like a row with a bad
+// time and reports MTG_TRAJ_BAD_SEGMENTS.  There is one path to the end for
+// every row: with a return ahead of the IPM the N = 10 kernels spill more
+// (DESIGN.md 5.10.3).  The pad is 0.0, and NaN for a row that has no result
+// at all (not a trajectory, or a bad time).
+//
+// ipm is &Tube<N>::ipm, passed by the kernel and called through the pointer.
+// The inliner works bottom-up: a direct call is inlined into this function on
+// its own and the result optimised once here and again inside the kernel,
+// which costs the N = 10 kernels 8 B of scratch per lane (72 and 68 B); the
+// pointer is a constant only once this function is inside the kernel, so the
+// IPM is inlined there, once (56 and 52 B).  What the
+// compiler makes of it shows in tools/kernel_regs.py on the two objects.
+template <int N>
+__device__ __attribute__((always_inline)) void tube_solve_one(
+    int S, int S_pad, bool valid, int r, const double* __restrict__ tab,
+    const double* __restrict__ positions, const double* __restrict__ fixed_vals,
+    const double* __restrict__ times_cp, const double* __restrict__ times,
+    const double* __restrict__ radii, double tol, int max_iter, double* __restrict__ x_out,
+    double* __restrict__ coeffs, int64_t q, double* __restrict__ cost,
+    int32_t* __restrict__ iters, int32_t* __restrict__ status, double* __restrict__ ws,
+    int32_t* __restrict__ warm_ok, TubeIpm<N> ipm) {
+  extern __shared__ __attribute__((aligned(16))) double smem[];
+  constexpr int M = N / 2;
+  const TubeLayout L = make_tube_layout(N, S);
+  Tube<N> t = make_tube<N>(&L, smem, S, r, tab);
+  int* bad = reinterpret_cast<int*>(smem + L.ndouble);
+  // One vertex (S = 2) has no coupling block: the layout still holds one
+  // M x M slot for it, Tube::setup writes none of it, and Tube::factor loads
+  // it with a clamped index and multiplies it by a role factor of 0.0.  What
+  // an earlier workgroup left there would enter as 0.0 x word: NaN where the
+  // word is NaN or inf, and then the pivot, the factorisation and the row's
+  // result would depend on what ran on the CU before.  Written here
+  // (workgroup-uniform; setup's barriers order it ahead of every factor()).
+  if (S == 2)
+    for (int i = t.tid; i < M * M; i += t.nthr) smem[L.Po + i] = 0.0;
+  t.setup(tab, 0, 0, positions, fixed_vals, times_cp, times, radii, bad);
+  int st = 1;
+  int it = 0;
+  // Warm start from the problem's last usable solve, where warm_ok[q].
+  const bool use_ws = ws && warm_ok[q];
+  if (valid && !(*bad & 1)) it = (t.*ipm)(tol, max_iter, &st, bad, use_ws ? ws : nullptr);
+  __syncthreads();
+  if (ws && valid && !(*bad & 3) && st != 2) {
+    t.save_state(ws);
+    if (t.tid == 0) warm_ok[q] = 1;
+  }
+  // Bit 0: a time is not positive; a row that is not a trajectory counts
+  // likewise: NaN over the whole padded row.  Bit 1: the start system is not
+  // positive definite, so x was never written: NaN over the row's values.
+  const int fl = *bad;
+  const bool dead = !valid || (fl & 1) != 0;
+  const bool no_x = dead || (fl & 2) != 0;
+  // The powers share LDS with the factors: recompute them for the outputs.
+  if (!dead) t.compute_powers();
+  __syncthreads();
+  // Outputs: x (reference order), coefficients (qcqp_impl:777-785 ->
+  // linear_impl:254-275) and computeCost (linear_impl:113-130).
+  // The solve is relative to tube_origin() (Tube::setup): x's positions and
+  // the constant coefficients go back to world coordinates; the cost is the
+  // relative problem's (a translation does not change it).
+  const int row = (S - 1) * M, row_pad = (S_pad - 1) * M;
+  if (x_out)
+    for (int idx = t.tid; idx < 3 * row_pad; idx += t.nthr) {
+      const int d = idx / row_pad, j = idx % row_pad;
+      double v = dead ? NAN : 0.0;
+      if (j < row) {
+        const int a = j / M, m = j % M;
+        v = smem[L.x + (a * 3 + d) * M + m];
+        v = no_x ? NAN : (m == 0 ? v + tube_origin(positions, 0, S, d) : v);
+      }
+      x_out[idx] = v;
+    }
+  const double* xv = smem + L.x;
+  double acc = 0.0;
+  const int per = S * 3 * N, per_pad = S_pad * 3 * N;
+  for (int i = t.tid; i < per; i += t.nthr) {
+    const int s = i / (3 * N), d = (i / N) % 3, k = i % N;
+    const int lk = k % M;
+    double c = 0.0, h = 0.0;
+#pragma unroll
+    for (int j = 0; j < N; ++j) {
+      const int l = j % M;
+      const double e = t.xval(xv, s + j / M, d, l);
+      c += tab[N * N + k * N + j] * t.pwr(s, l - k) * e;
+      h += tab[k * N + j] * t.pwr(s, 1 - 2 * r + lk + l) * e;
+    }
+    coeffs[i] = no_x ? NAN : (k == 0 ? c + tube_origin(positions, 0, S, d) : c);
+    acc += h * t.xval(xv, s + k / M, d, lk);
+  }
+  for (int i = per + t.tid; i < per_pad; i += t.nthr) coeffs[i] = dead ? NAN : 0.0;
+  const double J = 0.5 * t.block_sum(acc);
+  if (t.tid == 0) {
+    if (cost) cost[q] = no_x ? NAN : J;
+    if (iters) iters[q] = it;
+    if (status)
+      status[q] = !valid                ? MTG_TRAJ_BAD_SEGMENTS
+                : (fl & 1)             ? MTG_TRAJ_BAD_TIME
+                : ((fl & 2) || st == 2) ? MTG_TRAJ_NOT_SPD
+                : st == 0              ? MTG_TRAJ_OK
+                : st == 3              ? MTG_TRAJ_NEAR_OPTIMAL
+                                       : MTG_TRAJ_NOT_CONVERGED;
+  }
+}
+
 }  // namespace mtg

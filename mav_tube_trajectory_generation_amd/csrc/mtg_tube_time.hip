@@ -190,9 +190,6 @@ __global__ void tube_time_opt_final_kernel(int S, int64_t B, OptState s,
 // trajectory b lives in the workspace and one thread advances it between
 // rounds.  NLopt evaluates T0 first, so the initial solveQCQP (:342) is the
 // first round's solve.
-__device__ inline sbplx::State* sb_state(const OptState& s, int64_t b) {
-  return reinterpret_cast<sbplx::State*>(s.sb + static_cast<size_t>(b) * s.sb_bytes);
-}
 
 __global__ void tube_time_sbplx_init_kernel(int S, int64_t B, const double* __restrict__ times,
                                             double step_rel, int max_evals, double ftol_rel,
@@ -211,18 +208,12 @@ __global__ void tube_time_sbplx_init_kernel(int S, int64_t B, const double* __re
   s.warm_ok[b] = 0;  // the first evaluation (T0) starts cold
 }
 
-// Hand the round's J to the machine; it writes the next point into Ttr or
-// finishes.  The QCQP status of the first evaluation (T0) is the one
-// reported.
+// The machine's step between rounds (tube_time_sbplx_step_body,
+// mtg_tube_time_shared.h).
 __global__ void tube_time_sbplx_step_kernel(int S, int64_t B, int first,
                                             const double* __restrict__ Jall,
                                             const int32_t* __restrict__ qstatus, OptState s) {
-  const int64_t b = static_cast<int64_t>(blockIdx.x) * blockDim.x + threadIdx.x;
-  if (b >= B || s.done[b]) return;
-  if (first) s.st[b] = qstatus[b];
-  sbplx::Machine m{sb_state(s, b)};
-  m.resume(Jall[b], s.Ttr + b * S);
-  if (m.s->done) s.done[b] = 1;
+  tube_time_sbplx_step_body(S, B, first, Jall, qstatus, s);
 }
 
 // NLopt's x and opt_f (the best point and its value), the evaluations used

@@ -1,10 +1,13 @@
 // mtg_tube_time_shared.h — what the tube QCQP time optimisers of uniform and of
 // ragged batches (mtg_tube_time.hip, mtg_ragged_tube_time.hip) share: the
-// dispatch-order sort, the workspace carver and the small kernels' grid size.
+// dispatch-order sort, the LN_SBPLX step, the workspace carver and the small
+// kernels' grid size.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stddef.h>
 #include <stdint.h>
+
+#include "mtg_sbplx_device.h"
 
 namespace mtg {
 
@@ -40,6 +43,28 @@ __device__ __attribute__((always_inline)) inline void tube_time_order_body(
   __syncthreads();
   for (int64_t b = t; b < B; b += blockDim.x)
     order[atomicAdd(&off[key(b)], 1)] = static_cast<int32_t>(b);
+}
+
+// The LN_SBPLX machine (mtg_sbplx_device.h) of trajectory b in the workspace;
+// State is the file's OptState (sb: the machines, sb_bytes each).
+template <typename State>
+__device__ inline sbplx::State* sb_state(const State& s, int64_t b) {
+  return reinterpret_cast<sbplx::State*>(s.sb + static_cast<size_t>(b) * s.sb_bytes);
+}
+
+// Hand the round's J to the machine; it writes the next point into Ttr (rows
+// of `stride`) or finishes.  The QCQP status of the first evaluation (T0) is
+// the one reported.  The body of a kernel of one thread per trajectory.
+template <typename State>
+__device__ __attribute__((always_inline)) inline void tube_time_sbplx_step_body(
+    int stride, int64_t B, int first, const double* __restrict__ Jall,
+    const int32_t* __restrict__ qstatus, const State& s) {
+  const int64_t b = static_cast<int64_t>(blockIdx.x) * blockDim.x + threadIdx.x;
+  if (b >= B || s.done[b]) return;
+  if (first) s.st[b] = qstatus[b];
+  sbplx::Machine m{sb_state(s, b)};
+  m.resume(Jall[b], s.Ttr + b * stride);
+  if (m.s->done) s.done[b] = 1;
 }
 
 inline unsigned blocks_for(int64_t n) { return static_cast<unsigned>((n + 255) / 256); }

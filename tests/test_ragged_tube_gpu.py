@@ -396,3 +396,46 @@ def test_chain(ctx, dev, case1):
     want = int(np.argmin(np.where(feasible, cost, np.inf)))
     got = triple.cpu().numpy()
     assert (got[0], int(got[1]), int(got[2])) == (cost[want], want, 0)
+
+
+def _random_rows(n, S, S_max, B, dev, seed0):
+    """Padded device inputs of B random rows of count S (the bench generator;
+    the padding NaN)."""
+    import mav_tube_trajectory_generation_amd as mtg
+    m = n // 2
+    _, _, times, pos = mtg.generate_random_problems(n, 3, S, B, seed0=seed0)
+    a = dict(seg_counts=np.full(B, S, np.int32), positions=np.full((B, S_max + 1, 3), np.nan),
+             fixed_vals=np.zeros((B, 3, n)), times_cp=np.full((B, S_max), np.nan),
+             times=np.full((B, S_max), np.nan), radii=np.full((B, S_max, 2), np.nan))
+    a["positions"][:, :S + 1] = pos
+    a["fixed_vals"][:, :, 0] = pos[:, 0, :]
+    a["fixed_vals"][:, :, m] = pos[:, S, :]
+    a["times_cp"][:, :S] = times
+    a["times"][:, :S] = times
+    a["radii"][:, :S] = RADIUS
+    return {k: torch.from_numpy(v).to(dev) for k, v in a.items()}
+
+
+def test_two_segment_rows_ignore_stale_lds(ctx, dev):
+    """Rows of count 2 do not depend on what the CU ran before
+    (tests/test_tube_gpu.py, the test of the same name, has the layout
+    arithmetic: Po of a two-segment row is doubles [144, 169), inside the
+    geometry [104, 180) of a four-segment row).  Both launches carve their rows
+    from the same allocation (S_max = 8), so a workgroup's layout starts where
+    its predecessor's did.  The rows of count 2 are solved after benign rows of
+    count 4 and after rows of count 4 whose vertex positions are NaN."""
+    n, r, S_max, B = 10, 4, 8, 2048
+    two = _random_rows(n, 2, S_max, B, dev, 9100)
+    four = _random_rows(n, 4, S_max, B, dev, 9100)
+    nan4 = dict(four, positions=torch.full_like(four["positions"], float("nan")))
+    runs = []
+    import mav_tube_trajectory_generation_amd as mtg
+    for before in (four, nan4):
+        first = mtg.ragged_tube_solve(ctx, n, r, **before)  # no wait between the two
+        runs.append((host(solve(ctx, n, r, two)), host(first)))
+    (a, _), (b, poison) = runs
+    assert (poison["status"] == 2).all() and np.isnan(poison["cost"]).all()
+    for k in ("x", "coeffs", "cost", "iters", "status"):
+        assert same_bits(a[k], b[k]), k
+    for k in ("x", "coeffs", "cost"):
+        assert np.isfinite(b[k]).all(), k

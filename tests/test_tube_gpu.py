@@ -196,3 +196,54 @@ def test_compile_time_s_kernels_vs_oracle(ctx, dev, oracle, S):
             continue
         assert rel_err_coeffs(out["coeffs"][b], ref["coeffs"]) <= 1e-6, (S, b)
         assert rel_err(out["cost"][b], ref["cost"]) <= 1e-6, (S, b)
+
+
+def _random_tube_batch(S, B, dev, seed0):
+    """Device inputs of B random S-segment problems (the bench generator)."""
+    import mav_tube_trajectory_generation_amd as mtg
+    _, _, times, pos = mtg.generate_random_problems(N, 3, S, B, seed0=seed0)
+    fv = np.zeros((B, 3, N))
+    fv[:, :, 0] = pos[:, 0, :]
+    fv[:, :, M] = pos[:, S, :]
+    T = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)  # noqa: E731
+    return dict(positions=T(pos), fixed_vals=T(fv), times_cp=T(times), times=T(times),
+                radii=torch.full((B, S, 2), 0.15, dtype=torch.float64, device=dev))
+
+
+def test_two_segment_rows_ignore_stale_lds(ctx, dev):
+    """An S = 2 solve does not depend on what the CU ran before.  With one
+    free vertex the layout's coupling slot Po is written by nobody but the
+    solve body's own zeroing (tube_solve_one, mtg_tube_device.h), and
+    Tube::factor multiplies its words by 0.0: a NaN left there by an earlier
+    workgroup used to become the pivot.
+
+    The S = 2 batch is solved twice: after a benign S = 4 solve, and after an
+    S = 4 solve whose vertex positions are NaN.  make_tube_layout(10, .), in
+    doubles: at S = 2 Po is [144, 169) (bul 50, T 2, geo 38, fixv 30, pos 9,
+    Pd 15 before it); at S = 4 the per-segment geometry is [104, 180) (bul
+    100, T 4 before it), every word of it computed from the positions, so NaN
+    in the second run.  LDS is not cleared between launches and B = 2048
+    workgroups land on every CU several times.  The two launches allocate
+    different amounts of LDS, so only a CU's first workgroup slot is certain
+    to start where its predecessor's did (the ragged test of the same name has
+    equal allocations); one such slot per CU is what the test needs.  The NaN batch takes the
+    MTG_TRAJ_NOT_SPD path of any non-finite input (one iteration, NaN
+    outputs)."""
+    import mav_tube_trajectory_generation_amd as mtg
+    B = 2048
+    two = _random_tube_batch(2, B, dev, 9000)
+    four = _random_tube_batch(4, B, dev, 9000)
+    nan4 = dict(four, positions=torch.full_like(four["positions"], float("nan")))
+    runs = []
+    for before in (four, nan4):
+        first = mtg.tube_solve(ctx, N, R, **before)
+        out = mtg.tube_solve(ctx, N, R, **two)
+        torch.cuda.synchronize()
+        runs.append(({k: v.cpu().numpy() for k, v in first.items()},
+                     {k: v.cpu().numpy() for k, v in out.items()}))
+    (_, a), (poison, b) = runs
+    assert (poison["status"] == 2).all() and np.isnan(poison["cost"]).all()
+    for k in a:
+        assert a[k].tobytes() == b[k].tobytes(), k
+    for k in ("x", "coeffs", "cost"):
+        assert np.isfinite(b[k]).all(), k
