@@ -1072,6 +1072,72 @@ int mtg_coll_optimize_trace(const mtg_plan* plan, int64_t B, int mode, const dou
                             size_t workspace_bytes, void* stream);
 
 /* ------------------------------------------------------------------------
+ * Ragged collision objectives: mtg_coll_cost and mtg_coll_optimize_trace over
+ * rows with their own segment counts, one call for the whole batch.  D = 3 and
+ * the tube pattern only: start and end vertex fix derivatives 0..M-1 (M = N/2),
+ * every intermediate derivative is free: the pattern whose free values
+ * mtg_ragged_tube_solve returns as x.  Plan-free; ctx supplies the (N, r)
+ * tables.  With np_max = (S_max - 1) M, all on the device:
+ *   seg_counts  B              int32, 2 <= S_b <= S_max, read by kernels only
+ *   fixed_vals  B x 3 x N      as mtg_ragged_tube_solve
+ *   times       B x S_max      mode 0 only; the first S_b are read
+ * x, x_io, grad, lower, upper, initial_step and every row of x_history
+ * (B x max_evals x nv_max) share one layout:
+ *   mode 0  B x 3 x np_max: row d holds the (S_b - 1) M values of dimension
+ *           d, then padding: exactly mtg_ragged_tube_solve's x;
+ *   mode 1  B x (S_max + 3 np_max): S_max times, of which the first S_b are
+ *           used, then the mode-0 block.
+ * The padding of every input may be NaN and is never read.  grad padding is
+ * written 0.0, x_io padding keeps its bits, the padding of a written
+ * x_history row is 0.0.
+ *
+ * Per row, cost, grad, terms (B x 4), collision, evals, result, status and the
+ * optimised point are those of mtg_coll_cost / mtg_coll_optimize_trace on the
+ * row's first S_b segments: the same objective, raise rule, difference
+ * schemes, soft constraints, projected L-BFGS and stopping codes.
+ *
+ * The host never reads the counts.  A row whose count is outside [2, S_max]
+ * gets status MTG_TRAJ_BAD_SEGMENTS: cost, terms and the whole padded grad row
+ * NaN and collision -1; the optimiser gives it evals 0, result -1 and leaves
+ * x_io untouched.  A non-positive time among the first S_b behaves as in the
+ * uniform entries (MTG_TRAJ_BAD_TIME).  Either kind of row touches nothing
+ * outside itself.
+ *
+ * Scratch: `workspace` is a caller-owned device buffer of at least
+ * mtg_ragged_coll_workspace_bytes(N, S_max, B, mode, params, optimize) bytes;
+ * every word of it is written by the call before it is read.  No call
+ * allocates or synchronises, so each can be captured in a HIP graph and
+ * replayed over other counts, points and maps of the same size.
+ *
+ * Checks, in this order: N, r, mode, S_max >= 2, B >= 0 and B x (problems per
+ * row) <= 2^31 - 1, problems per row = max(P_max, Q_max) of the row of S_max
+ * (MTG_ERR_INVALID_ARG); S_max <= 64, the prep kernel's LDS of the largest
+ * layout of 2..S_max and the walk's within 64 KiB (MTG_ERR_UNSUPPORTED);
+ * params as the uniform entries check them, and the grid sizes
+ * (MTG_ERR_INVALID_ARG); max_evals positive; all before ctx or any pointer is
+ * looked at.  Then NULL ctx or a NULL required pointer with B > 0.  B == 0
+ * returns MTG_OK and launches nothing; a NULL or too small workspace is
+ * MTG_ERR_INVALID_ARG.  The query returns the (negative) code of the first
+ * failed size or parameter check. */
+int64_t mtg_ragged_coll_workspace_bytes(int N, int S_max, int64_t B, int mode,
+                                        const mtg_coll_params* params, int optimize);
+int mtg_ragged_coll_cost(mtg_ctx* ctx, int N, int r, int S_max, int64_t B, int mode,
+                         const int32_t* seg_counts, const double* fixed_vals, const double* x,
+                         const double* times, const float* occupancy, int nx, int ny, int nz,
+                         const uint16_t* near_field, const mtg_coll_params* params,
+                         const double* raise_ref, double* cost, double* grad, double* terms,
+                         int32_t* collision, int32_t* status, void* workspace,
+                         size_t workspace_bytes, void* stream);
+int mtg_ragged_coll_optimize(mtg_ctx* ctx, int N, int r, int S_max, int64_t B, int mode,
+                             const int32_t* seg_counts, const double* fixed_vals, double* x_io,
+                             const double* times, const double* lower, const double* upper,
+                             const double* initial_step, const float* occupancy, int nx, int ny,
+                             int nz, const uint16_t* near_field, const mtg_coll_params* params,
+                             int max_evals, double* cost, int32_t* evals, int32_t* result,
+                             int32_t* status, double* terms, double* x_history, void* workspace,
+                             size_t workspace_bytes, void* stream);
+
+/* ------------------------------------------------------------------------
  * Selection for the multi-GPU path (BASELINE config 4: the
  * shards solve independently and the ranks all-gather costs for
  * selection).  mtg_select_local reduces rank `rank`'s shard of `count`

@@ -12,7 +12,8 @@ from .batch import (Context, LinearPlan, RaggedLinearPlan, coll_field,  # noqa: 
                     generate_random_problems,
                     magnitude_candidates,
                     max_magnitude,
-                    min_max_magnitude, pack_ragged, pack_ragged_tube, ragged_collision_cost,
+                    min_max_magnitude, pack_ragged, pack_ragged_tube, ragged_coll_cost,
+                    ragged_coll_optimize, ragged_coll_workspace_bytes, ragged_collision_cost,
                     ragged_max_magnitude,
                     ragged_sample_trajectories, ragged_soft_constraint_cost,
                     ragged_tube_num_constraints, ragged_tube_residuals, ragged_tube_solve,
@@ -29,6 +30,7 @@ __all__ = ["Context", "LinearPlan", "RaggedLinearPlan", "pack_ragged", "MTGError
            "max_magnitude",
            "min_max_magnitude", "make_coll_params", "make_collision_params", "make_time_params",
            "COLL_DEFAULTS",
+           "ragged_coll_cost", "ragged_coll_optimize", "ragged_coll_workspace_bytes",
            "ragged_collision_cost", "ragged_max_magnitude", "ragged_sample_trajectories", "ragged_soft_constraint_cost",
            "pack_ragged_tube", "ragged_tube_num_constraints", "ragged_tube_residuals",
            "ragged_tube_solve", "ragged_tube_time_cost", "ragged_tube_time_optimize",

@@ -282,6 +282,22 @@ SIGNATURES = {
                                                      ctypes.POINTER(TimeParams), ctypes.c_int,
                                                      _vp, _vp, _vp, _vp, _vp, ctypes.c_size_t,
                                                      _vp]),
+    "mtg_ragged_coll_workspace_bytes": (ctypes.c_int64, [ctypes.c_int, ctypes.c_int,
+                                                         ctypes.c_int64, ctypes.c_int,
+                                                         ctypes.POINTER(CollObjectiveParams),
+                                                         ctypes.c_int]),
+    "mtg_ragged_coll_cost": (ctypes.c_int, [_vp, ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                                            ctypes.c_int64, ctypes.c_int, _vp, _vp, _vp, _vp, _vp,
+                                            ctypes.c_int, ctypes.c_int, ctypes.c_int, _vp,
+                                            ctypes.POINTER(CollObjectiveParams), _vp, _vp, _vp,
+                                            _vp, _vp, _vp, _vp, ctypes.c_size_t, _vp]),
+    "mtg_ragged_coll_optimize": (ctypes.c_int, [_vp, ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                                                ctypes.c_int64, ctypes.c_int, _vp, _vp, _vp, _vp,
+                                                _vp, _vp, _vp, _vp, ctypes.c_int, ctypes.c_int,
+                                                ctypes.c_int, _vp,
+                                                ctypes.POINTER(CollObjectiveParams),
+                                                ctypes.c_int, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
+                                                ctypes.c_size_t, _vp]),
     "mtg_select_local": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64,
                                          ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p]),
     "mtg_select_workspace_bytes": (ctypes.c_int64, [_vp, ctypes.c_int64]),

@@ -1188,6 +1188,123 @@ def ragged_tube_time_optimize(ctx, N, r, seg_counts, positions, fixed_vals, radi
     return dict(times=t, cost=cost, evals=evals, result=result, status=status)
 
 
+def ragged_coll_workspace_bytes(N, S_max, B, params, mode=0, optimize=False):
+    """Device scratch the ragged collision objective / optimiser needs
+    (mtg_ragged_coll_workspace_bytes)."""
+    n = lib().mtg_ragged_coll_workspace_bytes(N, S_max, B, mode, ctypes.byref(params),
+                                              1 if optimize else 0)
+    if n < 0:
+        check(int(n), "mtg_ragged_coll_workspace_bytes")
+    return int(n)
+
+
+def _ragged_coll_inputs(N, seg_counts, fixed_vals, x, times, occupancy, mode, S_max):
+    """Shapes of the ragged collision entries.  Mode 0: x [B, 3, np_max] (as
+    ragged_tube_solve's x) and times [B, S_max]; mode 1: x [B, S_max +
+    3 np_max] and S_max given (times is not read)."""
+    import torch
+    M = N // 2
+    if mode == 0:
+        if not isinstance(times, torch.Tensor) or times.dim() != 2:
+            raise MTGError("times must be a CUDA tensor [B, S_max]")
+        B, S_max = times.shape
+        _require(times, (B, S_max), "times")
+        _require(x, (B, 3, (S_max - 1) * M), "x")
+    else:
+        if S_max is None:
+            raise MTGError("mode 1 needs S_max")
+        if not isinstance(x, torch.Tensor) or x.dim() != 2:
+            raise MTGError("x must be a CUDA tensor [B, S_max + 3 (S_max - 1) M]")
+        B = x.shape[0]
+        _require(x, (B, S_max + 3 * (S_max - 1) * M), "x")
+    _require(fixed_vals, (B, 3, N), "fixed_vals")
+    _require_counts(seg_counts, B)
+    if not (isinstance(occupancy, torch.Tensor) and occupancy.is_cuda and
+            occupancy.dtype == torch.float32 and occupancy.dim() == 3 and
+            occupancy.is_contiguous()):
+        raise MTGError("occupancy must be a contiguous float32 CUDA tensor [nz, ny, nx]")
+    return B, int(S_max)
+
+
+def ragged_coll_cost(ctx, N, r, seg_counts, fixed_vals, x, times, occupancy, params, mode=0,
+                     raise_ref=None, grad=True, workspace=None, near_field=None, S_max=None):
+    """LinearPlan.coll_cost over a ragged batch of the tube pattern in one call
+    (mtg_ragged_coll_cost): row b is the objective of its first S_b =
+    seg_counts[b] segments, 2 <= S_b <= S_max.
+
+    seg_counts [B] int32, fixed_vals [B, 3, N] (CUDA).  Mode 0: x [B, 3,
+    (S_max - 1) M], exactly ragged_tube_solve's x, and times [B, S_max]; mode
+    1: x [B, S_max + 3 (S_max - 1) M] (S_max times, then the mode-0 block),
+    times unused and S_max given.  The padding is never read.  Returns
+    dict(cost, grad (shaped as x; padding 0.0), terms [B, 4], collision,
+    status).  A row whose count is out of range has status 5, cost, terms and
+    its whole grad row NaN and collision -1.  The counts stay on the device."""
+    import torch
+    B, S_max = _ragged_coll_inputs(N, seg_counts, fixed_vals, x, times, occupancy, mode, S_max)
+    _check_field(near_field, occupancy)
+    if raise_ref is not None:
+        _require(raise_ref, (B,), "raise_ref")
+    dev = x.device
+    nz, ny, nx = occupancy.shape
+    cost = torch.empty(B, dtype=torch.float64, device=dev)
+    g = torch.empty(x.shape, dtype=torch.float64, device=dev) if grad else None
+    terms = torch.empty((B, 4), dtype=torch.float64, device=dev)
+    coll = torch.empty(B, dtype=torch.int32, device=dev)
+    st = torch.empty(B, dtype=torch.int32, device=dev)
+    nb = ragged_coll_workspace_bytes(N, S_max, B, params, mode, False)
+    ws = _workspace(workspace, nb, dev)
+    check(lib().mtg_ragged_coll_cost(
+        ctx.handle, N, r, S_max, B, mode, _ptr(seg_counts), _ptr(fixed_vals), _ptr(x),
+        _ptr(times) if mode == 0 else None, _ptr(occupancy), nx, ny, nz, _ptr(near_field),
+        ctypes.byref(params), _ptr(raise_ref), _ptr(cost), _ptr(g), _ptr(terms), _ptr(coll),
+        _ptr(st), _ptr(ws), ws.numel() * ws.element_size(), _stream(dev)),
+        "mtg_ragged_coll_cost")
+    return dict(cost=cost, grad=g, terms=terms, collision=coll, status=st)
+
+
+def ragged_coll_optimize(ctx, N, r, seg_counts, fixed_vals, x0, times, occupancy, params, mode=0,
+                         max_evals=25, lower=None, upper=None, initial_step=None,
+                         workspace=None, near_field=None, history=False, S_max=None):
+    """LinearPlan.coll_optimize over a ragged batch of the tube pattern in one
+    call (mtg_ragged_coll_optimize): row b runs the projected L-BFGS over the
+    variables of its first S_b segments.  Inputs as ragged_coll_cost; lower,
+    upper and initial_step are shaped as x0.  Returns dict(x, cost, evals,
+    result, status, terms) with new tensors (the padding of x keeps x0's
+    bits); with history=True also x_history [B, max_evals, nv_max], each row
+    laid out as x0 flattened (the padding of a written row is 0.0, rows past
+    evals are unset).  A row whose count is out of range has status 5, cost
+    NaN, evals 0, result -1 and its x unchanged."""
+    import torch
+    B, S_max = _ragged_coll_inputs(N, seg_counts, fixed_vals, x0, times, occupancy, mode, S_max)
+    _check_field(near_field, occupancy)
+    for a, name in ((lower, "lower"), (upper, "upper"), (initial_step, "initial_step")):
+        if a is not None:
+            _require(a, tuple(x0.shape), name)
+    dev = x0.device
+    nv = x0[0].numel() if B else S_max * (mode != 0) + 3 * (S_max - 1) * (N // 2)
+    nz, ny, nx = occupancy.shape
+    x = x0.clone()
+    cost = torch.empty(B, dtype=torch.float64, device=dev)
+    ev = torch.empty(B, dtype=torch.int32, device=dev)
+    res = torch.empty(B, dtype=torch.int32, device=dev)
+    st = torch.empty(B, dtype=torch.int32, device=dev)
+    terms = torch.empty((B, 4), dtype=torch.float64, device=dev)
+    nb = ragged_coll_workspace_bytes(N, S_max, B, params, mode, True)
+    ws = _workspace(workspace, nb, dev)
+    hist = (torch.full((B, max_evals, nv), float("nan"), dtype=torch.float64, device=dev)
+            if history else None)
+    check(lib().mtg_ragged_coll_optimize(
+        ctx.handle, N, r, S_max, B, mode, _ptr(seg_counts), _ptr(fixed_vals), _ptr(x),
+        _ptr(times) if mode == 0 else None, _ptr(lower), _ptr(upper), _ptr(initial_step),
+        _ptr(occupancy), nx, ny, nz, _ptr(near_field), ctypes.byref(params), max_evals,
+        _ptr(cost), _ptr(ev), _ptr(res), _ptr(st), _ptr(terms), _ptr(hist), _ptr(ws),
+        ws.numel() * ws.element_size(), _stream(dev)), "mtg_ragged_coll_optimize")
+    out = dict(x=x, cost=cost, evals=ev, result=res, status=st, terms=terms)
+    if history:
+        out["x_history"] = hist
+    return out
+
+
 def sample_trajectories(coeffs, times, dt, t_start=0.0, t_end=-1.0, max_derivative=0,
                         n_max=None, with_times=True):
     """Batched Trajectory::evaluateRange (trajectory.cpp:74-134) for derivatives

@@ -594,17 +594,24 @@ int mtg_soft_constraint_cost(int N, int D, int S, int64_t B, const double* coeff
   return from_hip(mtg::launch_soft_cost_any(N, D, S, B, coeffs, times, spec, maxima, cost, st));
 }
 
-static bool valid_coll_params(const mtg_plan* plan, int mode, const mtg_coll_params* p) {
-  if (!plan || !p || (mode != 0 && mode != 1) || plan->dev.D != 3 || plan->dev.np < 1)
-    return false;
+// The optimiser, difference and soft-constraint parameters of the collision
+// objectives at polynomial order N.
+static bool valid_coll_params_at(int N, int mode, const mtg_coll_params* p) {
+  if (!p || (mode != 0 && mode != 1)) return false;
   if (p->lbfgs_memory < 1 || p->lbfgs_memory > 16 || p->n_soft < 0 ||
       p->n_soft > mtg::kMaxSoftConstraints)
     return false;
   if (mode == 1 && !(p->increment_time > 0.0)) return false;
   for (int c = 0; c < p->n_soft; ++c)
     if (p->soft_derivative[c] < 0 || p->soft_derivative[c] > mtg::kMaxExtremaDerivative ||
-        plan->dev.N - p->soft_derivative[c] - 1 <= 0 || !(p->soft_limit[c] > 0.0))
+        N - p->soft_derivative[c] - 1 <= 0 || !(p->soft_limit[c] > 0.0))
       return false;
+  return true;
+}
+
+static bool valid_coll_params(const mtg_plan* plan, int mode, const mtg_coll_params* p) {
+  if (!plan || plan->dev.D != 3 || plan->dev.np < 1) return false;
+  if (!valid_coll_params_at(plan->dev.N, mode, p)) return false;
   if (mtg::collision_lds_bytes(plan->dev.N, plan->dev.S) > 65536) return false;
   return true;
 }
@@ -1403,6 +1410,92 @@ int mtg_ragged_tube_time_optimize(mtg_ctx* ctx, int N, int r, int S_max, int64_t
   return mtg::ragged_tube_time_optimize(a, times_io, tol, max_iter, *params, max_evals, cost,
                                         evals, result, status, workspace, workspace_bytes,
                                         static_cast<hipStream_t>(stream));
+}
+
+// The ragged collision entries: sizes, then what the kernels support, then the
+// parameters and the grids, all before ctx or a pointer is looked at.
+static int ragged_coll_sizes(int N, int r, int S_max, int64_t B, int mode,
+                             const mtg_coll_params* params, int nx, int ny, int nz) {
+  if (!valid_N(N) || r < 0 || r > N / 2 - 1 || (mode != 0 && mode != 1) || S_max < 2 || B < 0 ||
+      B > 0x7fffffff)
+    return MTG_ERR_INVALID_ARG;
+  if (S_max > mtg::kMaxRaggedCollS ||
+      mtg::ragged_coll_prep_lds_bytes(N, S_max) > static_cast<size_t>(mtg::kMaxLdsBytes) ||
+      mtg::collision_lds_bytes(N, S_max) > 65536)  // the limit of mtg_ragged_collision_cost
+    return MTG_ERR_UNSUPPORTED;
+  if (!valid_coll_params_at(N, mode, params) ||
+      !valid_collision_params(params->coll, nx, ny, nz))
+    return MTG_ERR_INVALID_ARG;
+  if (mtg::ragged_coll_problems(N, S_max, B, mode, *params) > 0x7fffffff)
+    return MTG_ERR_INVALID_ARG;
+  return MTG_OK;
+}
+
+int64_t mtg_ragged_coll_workspace_bytes(int N, int S_max, int64_t B, int mode,
+                                        const mtg_coll_params* params, int optimize) {
+  const int rc = ragged_coll_sizes(N, N / 2 - 1, S_max, B, mode, params, 0, 0, 0);
+  if (rc) return rc;
+  return static_cast<int64_t>(
+      mtg::ragged_coll_workspace_bytes(N, S_max, B, mode, *params, optimize != 0));
+}
+
+// The pointers of both entries (x: the point or x_io).
+static int ragged_coll_args(mtg_ctx* ctx, int N, int r, int S_max, int64_t B, int mode,
+                            const int32_t* seg_counts, const double* fixed_vals, const double* x,
+                            const double* times, const float* occupancy, int nx, int ny, int nz,
+                            const uint16_t* near_field, mtg::RaggedCollArgs* a) {
+  if (!ctx || !seg_counts || !fixed_vals || !x || (mode == 0 && !times) ||
+      (!occupancy && static_cast<int64_t>(nx) * ny * nz > 0))
+    return MTG_ERR_INVALID_ARG;
+  const double* tab = nullptr;
+  const int rc = get_tables(ctx, N, r, &tab);
+  if (rc) return rc;
+  *a = mtg::RaggedCollArgs{N, r, S_max, B, mode, seg_counts, tab, fixed_vals, times, occupancy,
+                           nx, ny, nz, near_field};
+  return MTG_OK;
+}
+
+int mtg_ragged_coll_cost(mtg_ctx* ctx, int N, int r, int S_max, int64_t B, int mode,
+                         const int32_t* seg_counts, const double* fixed_vals, const double* x,
+                         const double* times, const float* occupancy, int nx, int ny, int nz,
+                         const uint16_t* near_field, const mtg_coll_params* params,
+                         const double* raise_ref, double* cost, double* grad, double* terms,
+                         int32_t* collision, int32_t* status, void* workspace,
+                         size_t workspace_bytes, void* stream) {
+  clear_stale_error();
+  int rc = ragged_coll_sizes(N, r, S_max, B, mode, params, nx, ny, nz);
+  if (rc) return rc;
+  if (B == 0) return MTG_OK;
+  mtg::RaggedCollArgs a;
+  rc = ragged_coll_args(ctx, N, r, S_max, B, mode, seg_counts, fixed_vals, x, times, occupancy,
+                        nx, ny, nz, near_field, &a);
+  if (rc) return rc;
+  if (!workspace) return MTG_ERR_INVALID_ARG;
+  return mtg::ragged_coll_cost(a, x, *params, raise_ref, cost, grad, terms, collision, status,
+                               workspace, workspace_bytes, static_cast<hipStream_t>(stream));
+}
+
+int mtg_ragged_coll_optimize(mtg_ctx* ctx, int N, int r, int S_max, int64_t B, int mode,
+                             const int32_t* seg_counts, const double* fixed_vals, double* x_io,
+                             const double* times, const double* lower, const double* upper,
+                             const double* initial_step, const float* occupancy, int nx, int ny,
+                             int nz, const uint16_t* near_field, const mtg_coll_params* params,
+                             int max_evals, double* cost, int32_t* evals, int32_t* result,
+                             int32_t* status, double* terms, double* x_history, void* workspace,
+                             size_t workspace_bytes, void* stream) {
+  clear_stale_error();
+  int rc = ragged_coll_sizes(N, r, S_max, B, mode, params, nx, ny, nz);
+  if (rc) return rc;
+  if (max_evals < 1) return MTG_ERR_INVALID_ARG;
+  if (B == 0) return MTG_OK;
+  mtg::RaggedCollArgs a;
+  rc = ragged_coll_args(ctx, N, r, S_max, B, mode, seg_counts, fixed_vals, x_io, times,
+                        occupancy, nx, ny, nz, near_field, &a);
+  if (rc) return rc;
+  if (!workspace) return MTG_ERR_INVALID_ARG;
+  return mtg::ragged_coll_optimize(a, x_io, lower, upper, initial_step, *params, max_evals, cost,
+                                   evals, result, status, terms, x_history, workspace,
+                                   workspace_bytes, static_cast<hipStream_t>(stream));
 }
 
 int mtg_generate_random_problems(int N, int D, int S, int64_t B, uint64_t seed0,

@@ -477,6 +477,38 @@ int coll_optimize(const PlanDev& pl, int64_t B, int mode, const double* df, doub
                   int32_t* result, int32_t* status, double* terms, double* x_history,
                   void* workspace, size_t workspace_bytes, hipStream_t st);
 
+// The same over a ragged batch of the tube pattern (mtg_ragged_coll_opt.hip):
+// coll_cost / coll_optimize per row with the row's own count, rows padded to
+// S_max.  D = 3.
+struct RaggedCollArgs {
+  int N, r, S_max;
+  int64_t B;
+  int mode;
+  const int32_t* seg_counts;  // B (device)
+  const double* tab;          // H(1), A(1)^-1 for (N, r)
+  const double* fixed_vals;   // B x 3 x N
+  const double* times;        // B x S_max (mode 0)
+  const float* occ;
+  int nx, ny, nz;
+  const uint16_t* field;      // nullable
+};
+constexpr int kMaxRaggedCollS = kMaxStdS;  // the rows the ragged extrema kernel stages
+// LDS of the prep kernel: the largest layout of the counts 2..S_max.
+size_t ragged_coll_prep_lds_bytes(int N, int S_max);
+size_t ragged_coll_workspace_bytes(int N, int S_max, int64_t B, int mode,
+                                   const mtg_coll_params& p, bool optimiser);
+// Workgroups of the widest launch (B x max(P_max, Q_max)).
+int64_t ragged_coll_problems(int N, int S_max, int64_t B, int mode, const mtg_coll_params& p);
+int ragged_coll_cost(const RaggedCollArgs& g, const double* x, const mtg_coll_params& p,
+                     const double* raise_ref, double* cost, double* grad, double* terms,
+                     int32_t* collision, int32_t* status, void* workspace,
+                     size_t workspace_bytes, hipStream_t st);
+int ragged_coll_optimize(const RaggedCollArgs& g, double* x_io, const double* lower,
+                         const double* upper, const double* initial_step,
+                         const mtg_coll_params& p, int max_evals, double* cost, int32_t* evals,
+                         int32_t* result, int32_t* status, double* terms, double* x_history,
+                         void* workspace, size_t workspace_bytes, hipStream_t st);
+
 // Multi-GPU selection (mtg_select.hip).
 hipError_t launch_select_local(const double* costs, int64_t count, int64_t start, int rank,
                                double* out, hipStream_t st);
