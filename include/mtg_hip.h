@@ -363,6 +363,68 @@ int mtg_ragged_time_optimize(const mtg_ragged_plan* plan, int64_t B, const int32
                              void* stream);
 
 /* ------------------------------------------------------------------------
+ * Ragged coefficients from constraints: mtg_coeffs_from_constraints
+ * (setFreeConstraints -> updateSegmentsFromCompactConstraints, then
+ * computeCost: linear_impl:254-275, 497-506, 113-130) over a ragged batch in
+ * one launch, for the two vertex patterns the ragged entries have.  Row b is
+ * what the uniform entry computes from the row's first S_b = seg_counts[b]
+ * segments: c = A_s^-1(T) [d(s); d(s+1)] per segment and dimension and
+ * cost = sum 0.5 c^T Q(T) c, summed from the coefficients.  It turns the
+ * free_vals of mtg_ragged_linear_solve (or an edited copy, or the same ones
+ * under the times of mtg_ragged_time_optimize) and the x of
+ * mtg_ragged_tube_solve / mtg_ragged_coll_optimize into what the ragged
+ * evaluators and mtg_ragged_collision_cost read.
+ *
+ * Standard pattern (mtg_ragged_coeffs_from_constraints): fixed_vals
+ * B x D x nf_max, free_vals B x D x np_max, np_max = (S_max - 1)(M - 1),
+ * times B x S_max, exactly the arrays of mtg_ragged_linear_solve;
+ * 1 <= S_b <= S_max.  free_vals may be NULL only where S_max == 1.
+ * Tube pattern (mtg_ragged_tube_coeffs; end vertices fixed to order M - 1,
+ * every derivative of the intermediate vertices free): fixed_vals B x D x N,
+ * 2 <= S_b <= S_max, and with np_max = (S_max - 1) M
+ *   layout 0  x B x D x np_max (row d: vertex 1..S_b - 1, derivative
+ *             0..M - 1) and times B x S_max, as mtg_ragged_tube_solve and
+ *             mtg_ragged_coll_optimize mode 0 write and read them;
+ *   layout 1  x B x (S_max + D np_max): each row [T; d_p] as
+ *             mtg_ragged_coll_optimize mode 1 writes it; times must be NULL.
+ * times_out (nullable, B x S_max) receives the row's S_b times contiguous
+ * and 0.0 behind them: the times array the evaluators take, whichever layout
+ * they came in.
+ *
+ * Outputs: coeffs B x S_max x D x N (16-byte aligned), segments < S_b as
+ * mtg_coeffs_from_constraints writes them and segments >= S_b written 0.0 by
+ * the same launch; cost and status B, nullable.  The input padding (fixed,
+ * free, times) is never read and may be NaN.  A row's results depend on its
+ * own data and count only, bit for bit: not on S_max, on its place in the
+ * batch or on the padding.  A count outside its range gives
+ * MTG_TRAJ_BAD_SEGMENTS, a time among the row's first S_b that is not
+ * positive (or NaN) MTG_TRAJ_BAD_TIME; either way coeffs over the whole
+ * padded row, cost and the times_out row are NaN and nothing outside the row
+ * is touched.  The counts are read on the device only.
+ *
+ * Checks, in this order: N in {4, 6, 8, 10, 12}, 1 <= D <= 4, 0 <= r < N/2,
+ * layout in {0, 1}, S_max >= 2 (the plan: >= 1), 0 <= B < 2^31
+ * (MTG_ERR_INVALID_ARG); S_max <= 64 (MTG_ERR_UNSUPPORTED); then NULL ctx or
+ * a NULL required pointer with B > 0, times given with layout 1 or missing
+ * with layout 0 (MTG_ERR_INVALID_ARG).  B == 0 returns MTG_OK and launches
+ * nothing.  No call allocates or synchronises (mtg_ragged_tube_coeffs takes
+ * the context's (N, r) table, which the context builds at its first use of
+ * (N, r), as for every tube entry); one 64-lane workgroup per row and under
+ * 7 KiB of LDS whatever S_max is.  The cost is summed operation for operation
+ * as mtg_coeffs_from_constraints sums it, from the same table, so a row's
+ * cost is the uniform entry's up to the rounding of the final sum over
+ * segments and dimensions, for every N. */
+int mtg_ragged_coeffs_from_constraints(const mtg_ragged_plan* plan, int64_t B,
+                                       const int32_t* seg_counts, const double* fixed_vals,
+                                       const double* free_vals, const double* times,
+                                       double* coeffs, double* cost, int32_t* status,
+                                       void* stream);
+int mtg_ragged_tube_coeffs(mtg_ctx* ctx, int N, int D, int r, int S_max, int64_t B, int layout,
+                           const int32_t* seg_counts, const double* fixed_vals, const double* x,
+                           const double* times, double* coeffs, double* cost, double* times_out,
+                           int32_t* status, void* stream);
+
+/* ------------------------------------------------------------------------
  * Ragged evaluators: mtg_max_magnitude, mtg_soft_constraint_cost and
  * mtg_sample_trajectories over the arrays a ragged solve writes, in one
  * launch each.  Plan-free, like their uniform counterparts (documented

@@ -16,7 +16,8 @@ from .batch import (Context, LinearPlan, RaggedLinearPlan, coll_field,  # noqa: 
                     ragged_coll_optimize, ragged_coll_workspace_bytes, ragged_collision_cost,
                     ragged_max_magnitude,
                     ragged_sample_trajectories, ragged_soft_constraint_cost,
-                    ragged_tube_num_constraints, ragged_tube_residuals, ragged_tube_solve,
+                    ragged_tube_coefficients, ragged_tube_num_constraints, ragged_tube_residuals,
+                    ragged_tube_solve,
                     ragged_tube_time_cost, ragged_tube_time_optimize,
                     ragged_tube_time_workspace_bytes,
                     sample_trajectories, segment_matrices,
@@ -32,7 +33,7 @@ __all__ = ["Context", "LinearPlan", "RaggedLinearPlan", "pack_ragged", "MTGError
            "COLL_DEFAULTS",
            "ragged_coll_cost", "ragged_coll_optimize", "ragged_coll_workspace_bytes",
            "ragged_collision_cost", "ragged_max_magnitude", "ragged_sample_trajectories", "ragged_soft_constraint_cost",
-           "pack_ragged_tube", "ragged_tube_num_constraints", "ragged_tube_residuals",
+           "pack_ragged_tube", "ragged_tube_coefficients", "ragged_tube_num_constraints", "ragged_tube_residuals",
            "ragged_tube_solve", "ragged_tube_time_cost", "ragged_tube_time_optimize",
            "ragged_tube_time_workspace_bytes",
            "sample_trajectories", "segment_matrices", "soft_constraint_cost",

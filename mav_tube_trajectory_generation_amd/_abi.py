@@ -210,6 +210,11 @@ SIGNATURES = {
     "mtg_ragged_plan_counts": (ctypes.c_int, [_vp, _ip, _ip]),
     "mtg_ragged_linear_solve": (ctypes.c_int, [_vp, ctypes.c_int64, _vp, _vp, _vp, _vp, _vp, _vp,
                                                _vp, _vp]),
+    "mtg_ragged_coeffs_from_constraints": (ctypes.c_int, [_vp, ctypes.c_int64, _vp, _vp, _vp, _vp,
+                                                          _vp, _vp, _vp, _vp]),
+    "mtg_ragged_tube_coeffs": (ctypes.c_int, [_vp, ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                                              ctypes.c_int, ctypes.c_int64, ctypes.c_int, _vp, _vp,
+                                              _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "mtg_ragged_time_cost": (ctypes.c_int, [_vp, ctypes.c_int64, _vp, _vp, _vp,
                                             ctypes.POINTER(TimeParams), _vp, _vp, _vp, _vp]),
     "mtg_ragged_time_optimize": (ctypes.c_int, [_vp, ctypes.c_int64, _vp, _vp, _vp,

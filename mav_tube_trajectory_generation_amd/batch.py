@@ -557,6 +557,42 @@ class RaggedLinearPlan:
                                             _stream(dev)), "mtg_ragged_linear_solve")
         return o
 
+    def coefficients(self, seg_counts, fixed_vals, free_vals, times, cost=True, status=True,
+                     out=None):
+        """LinearPlan.coefficients over the ragged batch in one launch
+        (mtg_ragged_coeffs_from_constraints): coefficients and cost from given
+        d_f and d_p, no solve.  free_vals [B, D, np_max] as solve(free=True)
+        returns it (None only where S_max == 1); the padding of the inputs is
+        never read.  Returns (coeffs [B, S_max, D, N] with segments >= S_b
+        0.0, cost [B] or None, status [B] int32 or None); out may supply
+        "coeffs", "cost" and "status".  A row whose count is outside
+        [1, S_max] (status 5) or with a non-positive time (status 1) has
+        coeffs and cost NaN."""
+        import torch
+        B = self._inputs(seg_counts, fixed_vals, times)
+        if free_vals is not None or self.S_max > 1:
+            _require(free_vals, (B, self.D, self.np_max), "free_vals")
+        dev = times.device
+        o = out or {}
+        if "coeffs" in o:
+            _require(o["coeffs"], (B, self.S_max, self.D, self.N), "coeffs")
+        if "cost" in o:
+            _require(o["cost"], (B,), "cost")
+        if "status" in o:
+            _require_int32(o["status"], (B,), "status")
+        if "coeffs" not in o:
+            o["coeffs"] = torch.empty((B, self.S_max, self.D, self.N), dtype=torch.float64,
+                                      device=dev)
+        if cost and "cost" not in o:
+            o["cost"] = torch.empty(B, dtype=torch.float64, device=dev)
+        if status and "status" not in o:
+            o["status"] = torch.empty(B, dtype=torch.int32, device=dev)
+        check(lib().mtg_ragged_coeffs_from_constraints(
+            self._h, B, _ptr(seg_counts), _ptr(fixed_vals), _ptr(free_vals), _ptr(times),
+            _ptr(o["coeffs"]), _ptr(o.get("cost")), _ptr(o.get("status")), _stream(dev)),
+            "mtg_ragged_coeffs_from_constraints")
+        return o["coeffs"], o.get("cost"), o.get("status")
+
     def time_cost(self, seg_counts, fixed_vals, times, time_penalty=500.0, grad_mode=0,
                   increment=0.1, w_d=0.1, w_t=1.0, soft=None, soft_weight=100.0, hard=False,
                   hard_tolerance=0.1):
@@ -1302,6 +1338,75 @@ def ragged_coll_optimize(ctx, N, r, seg_counts, fixed_vals, x0, times, occupancy
     out = dict(x=x, cost=cost, evals=ev, result=res, status=st, terms=terms)
     if history:
         out["x_history"] = hist
+    return out
+
+
+def ragged_tube_coefficients(ctx, N, r, seg_counts, fixed_vals, x, times=None, mode=0,
+                             S_max=None, out=None):
+    """Coefficients and cost of a ragged batch of the tube pattern from its
+    free derivatives in one launch (mtg_ragged_tube_coeffs): what
+    LinearPlan.coefficients gives per count, for row b over its first S_b =
+    seg_counts[b] segments, 2 <= S_b <= S_max.
+
+    seg_counts [B] int32, fixed_vals [B, D, N] (CUDA).  Mode 0: x [B, D,
+    (S_max - 1) M], as ragged_tube_solve and ragged_coll_optimize return it,
+    and times [B, S_max]; mode 1: x [B, S_max + D (S_max - 1) M], as
+    ragged_coll_optimize(mode=1) returns it, and times None.  S_max is taken
+    from the shapes (given, it must agree with them).  The padding is never
+    read.  Returns dict(coeffs [B, S_max, D, N] with segments >= S_b 0.0,
+    cost [B], status [B] int32) and in mode 1 also times [B, S_max]: each
+    row's S_b times, then 0.0; out may supply any of them (a "times" in out
+    is written in mode 0 as well).  A row whose count
+    is out of range (status 5) or with a non-positive time (status 1) has
+    coeffs, cost and times NaN.  The counts stay on the device."""
+    import torch
+    M = N // 2
+    if mode not in (0, 1):
+        raise MTGError("mode must be 0 or 1")
+    if not isinstance(fixed_vals, torch.Tensor) or fixed_vals.dim() != 3:
+        raise MTGError("fixed_vals must be a CUDA tensor [B, D, N]")
+    B, D = fixed_vals.shape[0], fixed_vals.shape[1]
+    _require(fixed_vals, (B, D, N), "fixed_vals")
+    if mode == 0:
+        if not isinstance(times, torch.Tensor) or times.dim() != 2:
+            raise MTGError("times must be a CUDA tensor [B, S_max]")
+        if S_max is not None and S_max != times.shape[1]:
+            raise MTGError(f"S_max = {S_max} but times has shape {tuple(times.shape)}")
+        S_max = times.shape[1]
+        _require(times, (B, S_max), "times")
+        _require(x, (B, D, (S_max - 1) * M), "x")
+    else:
+        if times is not None:
+            raise MTGError("mode 1 takes the times from x: times must be None")
+        if not isinstance(x, torch.Tensor) or x.dim() != 2:
+            raise MTGError("x must be a CUDA tensor [B, S_max + D (S_max - 1) M]")
+        if S_max is None:  # width = S_max (1 + D M) - D M
+            S_max, rem = divmod(x.shape[1] + D * M, 1 + D * M)
+            if rem:
+                raise MTGError(f"x has shape {tuple(x.shape)}: no S_max gives that width")
+        _require(x, (B, S_max + D * (S_max - 1) * M), "x")
+    S_max = int(S_max)
+    _require_counts(seg_counts, B)
+    dev = x.device
+    out = dict(out) if out is not None else {}
+    shapes = {"coeffs": (B, S_max, D, N), "cost": (B,)}
+    if mode == 1 or "times" in out:
+        shapes["times"] = (B, S_max)
+    for name, shp in shapes.items():  # the caller's outputs first, then the missing ones
+        if name in out:
+            _require(out[name], shp, name)
+    if "status" in out:
+        _require_int32(out["status"], (B,), "status")
+    for name, shp in shapes.items():
+        if name not in out:
+            out[name] = torch.empty(shp, dtype=torch.float64, device=dev)
+    if "status" not in out:
+        out["status"] = torch.empty(B, dtype=torch.int32, device=dev)
+    check(lib().mtg_ragged_tube_coeffs(
+        ctx.handle, N, D, r, S_max, B, mode, _ptr(seg_counts), _ptr(fixed_vals), _ptr(x),
+        _ptr(times) if mode == 0 else None, _ptr(out["coeffs"]), _ptr(out["cost"]),
+        _ptr(out.get("times")), _ptr(out["status"]), _stream(dev)),
+        "mtg_ragged_tube_coeffs")
     return out
 
 

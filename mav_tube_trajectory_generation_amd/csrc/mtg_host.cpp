@@ -983,6 +983,50 @@ int mtg_ragged_linear_solve(const mtg_ragged_plan* plan, int64_t B, const int32_
                                                   static_cast<hipStream_t>(stream)));
 }
 
+// mtg_coeffs_from_constraints over a ragged batch (setFreeConstraints ->
+// updateSegmentsFromCompactConstraints and computeCost, linear_impl:254-275,
+// 497-506, 113-130), standard pattern: the plan carries the sizes, checked
+// when it was made.
+int mtg_ragged_coeffs_from_constraints(const mtg_ragged_plan* plan, int64_t B,
+                                       const int32_t* seg_counts, const double* fixed_vals,
+                                       const double* free_vals, const double* times,
+                                       double* coeffs, double* cost, int32_t* status,
+                                       void* stream) {
+  clear_stale_error();
+  if (!plan || B < 0 || B > 0x7fffffff) return MTG_ERR_INVALID_ARG;
+  if (B == 0) return MTG_OK;
+  if (!seg_counts || !fixed_vals || !times || !coeffs || (!free_vals && plan->dev.S_max > 1))
+    return MTG_ERR_INVALID_ARG;
+  const mtg::RaggedCoeffsArgs a{plan->dev.N, plan->dev.D, plan->dev.r, plan->dev.S_max, B,
+                                plan->dev.tab, false, 0, seg_counts, fixed_vals, free_vals, times, coeffs,
+                                cost, nullptr, status};
+  return from_hip(mtg::launch_ragged_coeffs(a, static_cast<hipStream_t>(stream)));
+}
+
+// The same for the tube pattern (linear_impl:254-275, 497-506, 113-130): the
+// sizes first (they need neither a pointer nor a device), then ctx and the
+// pointers.  ctx gives the (N, r) table the cost is summed with, as for the
+// other tube entries (cached per context after its first use).
+int mtg_ragged_tube_coeffs(mtg_ctx* ctx, int N, int D, int r, int S_max, int64_t B, int layout,
+                           const int32_t* seg_counts, const double* fixed_vals, const double* x,
+                           const double* times, double* coeffs, double* cost, double* times_out,
+                           int32_t* status, void* stream) {
+  clear_stale_error();
+  if (!valid_N(N) || D < 1 || D > mtg::kMaxD || r < 0 || r > N / 2 - 1 ||
+      (layout != 0 && layout != 1) || S_max < 2 || B < 0 || B > 0x7fffffff)
+    return MTG_ERR_INVALID_ARG;
+  if (S_max > mtg::kMaxStdS) return MTG_ERR_UNSUPPORTED;
+  if (B && (!ctx || !seg_counts || !fixed_vals || !x || !coeffs)) return MTG_ERR_INVALID_ARG;
+  if (layout == 1 ? times != nullptr : (B && !times)) return MTG_ERR_INVALID_ARG;
+  if (B == 0) return MTG_OK;
+  const double* tab = nullptr;
+  const int rc = get_tables(ctx, N, r, &tab);
+  if (rc) return rc;
+  const mtg::RaggedCoeffsArgs a{N, D, r, S_max, B, tab, true, layout, seg_counts, fixed_vals, x,
+                                times, coeffs, cost, times_out, status};
+  return from_hip(mtg::launch_ragged_coeffs(a, static_cast<hipStream_t>(stream)));
+}
+
 // The ragged time entries: the coverage of the runtime-S standard time
 // kernels without soft or hard constraints, and the LDS for S_max checked
 // here, not met as a failure of the launch.

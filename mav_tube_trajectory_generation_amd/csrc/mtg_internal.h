@@ -129,6 +129,21 @@ hipError_t launch_ragged_time_optimize(const RaggedDev& pl, int64_t B, const int
 // LDS per workgroup: sized by S_max, whatever the trajectory's own count.
 size_t ragged_linear_lds_bytes(int N, int S_max, int D);
 size_t ragged_time_lds_bytes(int N, int S_max, int D, bool optimiser);
+// Coefficients and cost from given constraints over a ragged batch
+// (mtg_ragged_coeffs.hip), standard or tube pattern; layout 1 (tube only):
+// free_vals rows are [T; d_p] and times is unused.  No dynamic LDS.
+struct RaggedCoeffsArgs {
+  int N, D, r, S_max;
+  int64_t B;
+  const double* tab;  // H(1) then A(1)^-1, N*N each (device): the cost's table
+  bool tube;
+  int layout;
+  const int32_t* seg_counts;
+  const double *fixed_vals, *free_vals, *times;
+  double *coeffs, *cost, *times_out;  // cost, times_out nullable
+  int32_t* status;                    // nullable
+};
+hipError_t launch_ragged_coeffs(const RaggedCoeffsArgs& a, hipStream_t st);
 
 // Free-derivative objectives and optimiser (mtg_free.hip).
 hipError_t launch_free_cost(const PlanDev& pl, int64_t B, const double* df, const double* dp,
